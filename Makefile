@@ -5,7 +5,7 @@
 PY ?= python3
 HIPCC ?= /opt/rocm/bin/hipcc
 
-.PHONY: all build test test-par test-gpu test-real-apiserver bench demo lint coverage clean
+.PHONY: all build test test-par test-gpu test-real-apiserver bench bench-full demo lint coverage clean
 
 all: build test
 
@@ -46,6 +46,10 @@ test-real-apiserver:
 # Flagship benchmark (BASELINE config #3).
 bench:
 	$(PY) bench.py --steps 10 --warmup 2
+
+# Headline plus the comparison runs of the other two substrates.
+bench-full:
+	$(PY) bench.py --steps 10 --warmup 2 --full
 
 # Watch a full 8-node rolling upgrade against the mini-apiserver.
 demo:

@@ -10,8 +10,9 @@ The HEADLINE substrate is the production-shaped stack: state machine ->
 CachedClient (watch-fed informers) -> RestClient -> HTTP apiserver
 (``--substrate cached``, the default).  ``--substrate http`` drops the
 informer cache (direct REST), ``--substrate inproc`` is the round-1
-in-process dict store, kept for continuity; a single run reports all three
-(secondary substrates at reduced step count).
+in-process dict store, kept for continuity.  A plain run measures only the
+selected substrate; ``--full`` adds comparison runs of the other two
+(reduced step count) to the same JSON line.
 
 One *step* = one complete rolling upgrade of an 8-node cluster: every node
 travels upgrade-required -> cordon -> wait-for-jobs -> pod-deletion -> drain
@@ -34,6 +35,10 @@ Flags beyond the driver contract (--gpus/--steps/--warmup):
                    wait-for-jobs + xGMI-fabric validation hooks)
   --no-converge    strict reference semantics (one transition per tick)
   --no-gpu-validate  skip the native MFMA/xGMI checks in the validation step
+  --full           also run the comparison measurements (the two
+                   non-headline substrates); off by default
+  --dump-outputs DIR  write what the last timed step computed as
+                   DIR/<name>.npy (see collect_step_outputs)
 """
 
 from __future__ import annotations
@@ -327,6 +332,72 @@ def _run_gpu_validation(device, mode="inplace"):
     return max(err, bf16_err)
 
 
+# upgrade-state label values in lifecycle order; a node's final state is
+# dumped as its index here (so "upgrade-done" is 11.0)
+_STATE_ORDER = (
+    consts.UPGRADE_STATE_UNKNOWN,
+    consts.UPGRADE_STATE_UPGRADE_REQUIRED,
+    consts.UPGRADE_STATE_CORDON_REQUIRED,
+    consts.UPGRADE_STATE_WAIT_FOR_JOBS_REQUIRED,
+    consts.UPGRADE_STATE_POD_DELETION_REQUIRED,
+    consts.UPGRADE_STATE_DRAIN_REQUIRED,
+    consts.UPGRADE_STATE_NODE_MAINTENANCE_REQUIRED,
+    consts.UPGRADE_STATE_POST_MAINTENANCE_REQUIRED,
+    consts.UPGRADE_STATE_POD_RESTART_REQUIRED,
+    consts.UPGRADE_STATE_VALIDATION_REQUIRED,
+    consts.UPGRADE_STATE_UNCORDON_REQUIRED,
+    consts.UPGRADE_STATE_DONE,
+    consts.UPGRADE_STATE_FAILED,
+)
+
+
+def collect_step_outputs(sim, n_nodes, state_key, new_hash, validation_errs):
+    """What one finished rolling-upgrade step computed, as float64 arrays
+    indexed by node (``mi355x-0`` .. ``mi355x-<n-1>``), read from the
+    authoritative store before the step's cluster is torn down.
+
+    - ``node_final_state`` [n]: index of the node's upgrade-state label in
+      ``_STATE_ORDER`` (-1 if the label holds something else)
+    - ``node_unschedulable`` [n]: 1.0 if the node is still cordoned
+    - ``driver_pod_on_new_revision`` [n]: 1.0 if the node's driver pod
+      carries the new controller-revision hash
+    - ``workload_pods_remaining`` [n]: GPU workload pods left on the node
+    - ``gpu_validation_max_err`` [n]: the figure the node's native GPU
+      validation returned (max abs error of the MFMA f32/bf16 tiles vs the
+      CPU reference, or the slowest xGMI link's GB/s when the anic probe
+      found peers); -1.0 where no GPU validation ran
+
+    The cluster and the kernels' operands are fixed, so two runs with the
+    same arguments produce identical inputs and comparable outputs.
+    """
+    import numpy as np
+
+    names = [f"mi355x-{i}" for i in range(n_nodes)]
+    nodes = {n["metadata"]["name"]: n for n in sim.list("v1", "Node")}
+    pods = sim.list("v1", "Pod")
+    out = {k: np.zeros(n_nodes, dtype=np.float64) for k in (
+        "node_final_state", "node_unschedulable",
+        "driver_pod_on_new_revision", "workload_pods_remaining",
+        "gpu_validation_max_err")}
+    for i, name in enumerate(names):
+        node = nodes.get(name, {"metadata": {}})
+        label = (node["metadata"].get("labels") or {}).get(state_key, "")
+        out["node_final_state"][i] = (
+            _STATE_ORDER.index(label) if label in _STATE_ORDER else -1)
+        out["node_unschedulable"][i] = float(
+            bool((node.get("spec") or {}).get("unschedulable")))
+        on_node = [p for p in pods
+                   if (p.get("spec") or {}).get("nodeName") == name]
+        out["driver_pod_on_new_revision"][i] = float(any(
+            (p["metadata"].get("labels") or {}).get(
+                "controller-revision-hash") == new_hash for p in on_node))
+        out["workload_pods_remaining"][i] = sum(
+            1 for p in on_node
+            if (p["metadata"].get("labels") or {}).get("app") == "training")
+        out["gpu_validation_max_err"][i] = validation_errs.get(name, -1.0)
+    return out
+
+
 def _build_substrate(substrate):
     """Returns (client, sim_cluster, close_fn) for the requested substrate.
 
@@ -364,14 +435,15 @@ def _build_substrate(substrate):
 def run_rolling_upgrade_benchmark(
     n_nodes=8, steps=10, warmup=2, max_parallel=2, gpu_validate=False,
     device=0, gpu_pods_per_node=2, converge=True,
-    mode="inplace", substrate="cached",
+    mode="inplace", substrate="cached", collect_outputs=False,
 ):
     """Run `warmup` untimed + `steps` timed full rolling upgrades; returns a
     result dict (single-process path; bench main() adds distribution).
 
     ``converge=True`` uses the manager's converging reconcile (nodes travel
     every synchronously-completable transition per call); ``False`` uses the
-    reference's one-transition-per-tick semantics.
+    reference's one-transition-per-tick semantics.  ``collect_outputs=True``
+    adds ``outputs`` (see collect_step_outputs) for the last timed step.
     """
     from k8s_operator_libs_amd.metrics import MetricsRegistry
     from k8s_operator_libs_amd.upgrade.requestor import RequestorOptions
@@ -401,6 +473,7 @@ def run_rolling_upgrade_benchmark(
     tick_times = []
     ticks_per_upgrade = []
     completed = 0
+    outputs = None
 
     client, sim, close_substrate = _build_substrate(substrate)
     # in-process ops are microseconds: per-node fan-out is pure overhead
@@ -468,6 +541,7 @@ def run_rolling_upgrade_benchmark(
                 .with_pod_deletion_enabled(gpu_pod_deletion_filter)
                 .with_validation_enabled(VALIDATOR_SELECTOR)
             )
+            validation_errs = {}
             t0 = time.perf_counter()
             rounds = 0
             last_done = -1
@@ -505,7 +579,8 @@ def run_rolling_upgrade_benchmark(
                 for ns_ in state.nodes_in(consts.UPGRADE_STATE_VALIDATION_REQUIRED):
                     node_name = ns_.node["metadata"]["name"]
                     if gpu_validate:
-                        _run_gpu_validation(device, mode=mode)
+                        validation_errs[node_name] = _run_gpu_validation(
+                            device, mode=mode)
                     sim.patch(
                         "v1", "Pod", f"validator-{node_name}",
                         {"status": {"containerStatuses": [
@@ -547,6 +622,9 @@ def run_rolling_upgrade_benchmark(
                 ticks_per_upgrade.append(ticks)
                 completed += 1
             manager.wait_idle()
+            if collect_outputs and it == warmup + steps - 1:
+                outputs = collect_step_outputs(sim, n_nodes, state_key,
+                                               "newrev", validation_errs)
             ctrl.retarget({"metadata": {"uid": "-"}})
             cleanup()
             # iteration isolation: drain the previous cluster's DELETED
@@ -567,6 +645,7 @@ def run_rolling_upgrade_benchmark(
 
     return {
         "substrate": substrate,
+        "outputs": outputs,
         "upgrades_completed": completed,
         "mean_wall_s": statistics.mean(wall_times) if wall_times else 0.0,
         "wall_times": wall_times,
@@ -606,9 +685,19 @@ def main():
                              "(production-shaped, HEADLINE); http = direct "
                              "REST; inproc = round-1 dict store")
     parser.add_argument("--no-secondary-substrates", action="store_true",
-                        help="skip the reduced-step runs of the other two "
-                             "substrates (reported for comparison)")
+                        help="with --full: skip the reduced-step runs of the "
+                             "other two substrates")
+    parser.add_argument("--full", action="store_true",
+                        help="after the timed steps, also run the comparison "
+                             "measurements (reduced-step runs of the other "
+                             "two substrates) and report them under "
+                             "'substrates'")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="write what the last timed step computed as "
+                             "DIR/<name>.npy (float64, per node)")
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be at least 1")
 
     import torch
 
@@ -649,18 +738,26 @@ def main():
         max_parallel=args.max_parallel, gpu_validate=gpu_validate,
         device=local_rank if have_cuda else 0, converge=converge,
         mode=args.mode, substrate=args.substrate,
+        collect_outputs=bool(args.dump_outputs) and rank == 0,
     )
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
-    # comparison runs of the non-headline substrates (reduced step count,
-    # outside the timed region; rank 0 only)
+    if result["outputs"] is not None:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in result["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), arr)
+
+    # --full: comparison runs of the non-headline substrates (reduced step
+    # count, outside the timed region; rank 0 only)
     substrate_results = {args.substrate: {
         "mean_wall_s": result["mean_wall_s"],
         "reconcile_p50_ms": result["reconcile_p50_ms"],
         "steps": args.steps,
     }}
-    if rank == 0 and not args.no_secondary_substrates:
+    if rank == 0 and args.full and not args.no_secondary_substrates:
         for other in ("cached", "http", "inproc"):
             if other == args.substrate:
                 continue

@@ -34,6 +34,52 @@ def test_bench_cli_prints_contract_json():
     assert data["higher_is_better"] is False
     assert data["scaling"] == "weak"
     assert data["config"]["model"] == "amdgpu-driver-rolling-upgrade"
+    # a plain run measures the headline substrate only
+    assert data["steps"] == 2
+    assert list(data["substrates"]) == ["cached"]
+
+
+def test_bench_cli_full_and_dump_outputs(tmp_path):
+    """--full adds the comparison runs of the other two substrates;
+    --dump-outputs writes the last timed step's per-node results."""
+    import numpy as np
+
+    repo = os.path.join(os.path.dirname(__file__), "..")
+    dump = tmp_path / "dump"
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--steps", "1", "--warmup", "0",
+         "--nodes", "3", "--full", "--dump-outputs", str(dump)],
+        capture_output=True, text=True, cwd=repo, timeout=300,
+    )
+    assert out.returncode == 0, out.stderr
+    data = json.loads(out.stdout.strip().splitlines()[-1])
+    assert sorted(data["substrates"]) == ["cached", "http", "inproc"]
+    for sub in data["substrates"].values():
+        assert sub["mean_wall_s"] > 0
+    arrays = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert sorted(arrays) == [
+        "driver_pod_on_new_revision", "gpu_validation_max_err",
+        "node_final_state", "node_unschedulable", "workload_pods_remaining"]
+    for arr in arrays.values():
+        assert arr.dtype == np.float64 and arr.shape == (3,)
+    # every node finished: done, uncordoned, new driver, workloads evicted
+    assert (arrays["node_final_state"] == 11.0).all()
+    assert (arrays["node_unschedulable"] == 0.0).all()
+    assert (arrays["driver_pod_on_new_revision"] == 1.0).all()
+    assert (arrays["workload_pods_remaining"] == 0.0).all()
+
+
+def test_collect_outputs_only_on_request():
+    import bench
+
+    kwargs = dict(n_nodes=2, steps=1, warmup=0, max_parallel=1,
+                  gpu_validate=False, substrate="inproc")
+    assert bench.run_rolling_upgrade_benchmark(**kwargs)["outputs"] is None
+    outputs = bench.run_rolling_upgrade_benchmark(
+        collect_outputs=True, **kwargs)["outputs"]
+    assert outputs["node_final_state"].tolist() == [11.0, 11.0]
+    # no GPU validation ran
+    assert outputs["gpu_validation_max_err"].tolist() == [-1.0, -1.0]
 
 
 def test_bench_requestor_mode():
@@ -95,6 +141,11 @@ def test_bench_multirank_gloo_world4():
     repo = os.path.join(os.path.dirname(__file__), "..")
     env = dict(os.environ)
     env.setdefault("MASTER_ADDR", "127.0.0.1")
+    # this test is about the CPU/gloo path: hide any GPUs from the ranks, or
+    # a GPU box picks nccl and ranks 1-3 fail to bind a device that a
+    # single-GPU machine does not have
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    env["CUDA_VISIBLE_DEVICES"] = "-1"
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run",
          "--nnodes=1", "--nproc-per-node", "4",
