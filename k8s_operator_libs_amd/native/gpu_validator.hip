@@ -17,6 +17,8 @@
 //   hbm_bandwidth_gbps()  — nontemporal streaming copy (sweep-tuned, ~6 TB/s)
 //   lds_roundtrip_check() — LDS store/load/barrier integrity
 //   xgmi_p2p_probe()      — peer reachability + p2p bandwidth per xGMI link
+//   cu_coverage_check()   — f32/bf16/fp8 MFMA + LDS on every CU and SIMD,
+//                           exact, attributed per unit (opt-in sweep)
 //
 // Built standalone with hipcc (no torch linkage) via pybind11; the .so lives
 // in-tree so it travels to GPU nodes with the package.
@@ -30,6 +32,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -576,8 +579,399 @@ static py::list xgmi_p2p_probe(int device, double buf_mib, int iters) {
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Per-CU coverage sweep.  The single-wave MFMA smokes above exercise one
+// matrix pipe of 1024; this sweep runs the f32 / bf16 / fp8 tiles and an LDS
+// round trip in every wave of a grid sized to fill the device, and records
+// the result per (XCC, CU, SIMD) as the wave itself reads its placement from
+// HW_REG_HW_ID / HW_REG_XCC_ID.
+//
+// Operands are small integers (|v| <= 8, exact in f32, bf16 and e4m3), so
+// every K=32 dot product is an integer <= 2048 and exact in f32 in any
+// summation order: the comparison is bitwise, with no tolerance.
+//
+// Placement key (opaque; the field names are labels for humans only):
+//   key  = XCC_ID[3:0] << 8 | HW_ID[15:8]     (gfx9: cu[11:8] sh[12] se[15:13])
+//   simd = HW_ID[5:4]
+//   slot = key * 4 + simd                      -> 4096 * 4 = 16384 slots
+// The bit layout is an assumption; the host validates it by outcome (distinct
+// keys == multiProcessorCount, distinct slots == 4x that), never by trust.
+//
+// Every workgroup does a fixed amount of work and exits: no spins, no grid
+// barrier, no co-residency requirement.  The 64 KiB LDS claim caps a CU at
+// two workgroups (160 KiB / 64 KiB), so a grid of 2 x CUs that outlives the
+// launch skew is co-resident and lands two workgroups on every CU.  That only
+// makes one round the normal case; the host relaunches (bounded) otherwise.
+// ---------------------------------------------------------------------------
+
+constexpr int kCovSets = 4;                 // operand sets per repetition
+constexpr int kCovLdsWords = 16384;         // 64 KiB static LDS per workgroup
+constexpr int kCovKeys = 4096;              // 4 XCC bits + 8 HW_ID bits
+constexpr int kCovSlots = kCovKeys * 4;     // x 4 SIMDs
+constexpr int kCovBlock = 256;              // one wave per SIMD, normally
+constexpr int kCovBlocksPerCu = 2;          // floor(160 KiB / 64 KiB)
+constexpr unsigned kCovFailF32 = 1u, kCovFailBf16 = 2u, kCovFailFp8 = 4u,
+                   kCovFailLds = 8u;
+
+// s_getreg simm16 = id | offset << 6 | (size - 1) << 11; full 32 bits of each.
+constexpr int kCovHwRegHwId = 4 | (31 << 11);
+constexpr int kCovHwRegXccId = 20 | (31 << 11);
+
+// Per-lane record of one operand set, already in MFMA fragment order (the
+// layouts documented on the three smoke kernels above), packed by the host.
+struct CovLaneRec {
+  uint32_t f32_a, f32_b;        // A[l&15][l>>4], B[l>>4][l&15]
+  uint32_t bf16_a[4], bf16_b[4];  // 8 bf16: A[l&15][(l>>4)*8+i], B[(l>>4)*8+i][l&15]
+  uint32_t fp8_a[2], fp8_b[2];  // 8 e4m3, same geometry as bf16
+  uint32_t exp[3][4];           // expected D[(l>>4)*4+r][l&15] bits per dtype
+};
+constexpr int kCovRecWords = sizeof(CovLaneRec) / sizeof(uint32_t);
+
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+// second bound = waves per SIMD: two workgroups must fit on one CU
+__global__ void __launch_bounds__(kCovBlock, kCovBlocksPerCu)
+cu_coverage_kernel(const uint32_t* tab, uint32_t* __restrict__ slot_waves,
+                   uint32_t* __restrict__ slot_fail,
+                   uint32_t* __restrict__ slot_hw_id,
+                   uint32_t* __restrict__ slot_xcc_id, int reps, int poison_key,
+                   unsigned poison_mask, int poison_all) {
+#if defined(__gfx950__)
+  __shared__ uint32_t lds[kCovLdsWords];
+  const uint32_t hw_id = __builtin_amdgcn_s_getreg(kCovHwRegHwId);
+  const uint32_t xcc_id = __builtin_amdgcn_s_getreg(kCovHwRegXccId);
+  const uint32_t key = ((xcc_id & 0xFu) << 8) | ((hw_id >> 8) & 0xFFu);
+  const uint32_t simd = (hw_id >> 4) & 3u;
+
+  // test hook: data only, flips one bit of the *expected* values
+  const unsigned pm = (poison_all || (int)key == poison_key) ? poison_mask : 0u;
+  const uint32_t px[3] = {(pm >> 0) & 1u, (pm >> 1) & 1u, (pm >> 2) & 1u};
+  const uint32_t px_lds = (pm >> 3) & 1u;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  unsigned fail = 0;
+
+  for (int rep = 0; rep < reps; ++rep) {
+#pragma unroll 1
+    for (int s = 0; s < kCovSets; ++s) {
+      // volatile: operands and expected values are re-read from global memory
+      // every repetition, so neither the MFMAs nor the compares can be hoisted
+      const volatile uint32_t* p = tab + (size_t)(s * 64 + lane) * kCovRecWords;
+      const float fa = __uint_as_float(p[0]);
+      const float fb = __uint_as_float(p[1]);
+      u32x4 ba, bb;
+      for (int i = 0; i < 4; ++i) {
+        ba[i] = p[2 + i];
+        bb[i] = p[6 + i];
+      }
+      const uint64_t qa = (uint64_t)p[10] | ((uint64_t)p[11] << 32);
+      const uint64_t qb = (uint64_t)p[12] | ((uint64_t)p[13] << 32);
+
+      const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+      f32x4 d[3];
+      d[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa, fb, zero, 0, 0, 0);
+      d[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          __builtin_bit_cast(bf16x8, ba), __builtin_bit_cast(bf16x8, bb), zero,
+          0, 0, 0);
+      d[2] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8((long)qa, (long)qb,
+                                                        zero, 0, 0, 0);
+      for (int t = 0; t < 3; ++t)
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t want = p[14 + t * 4 + r] ^ px[t];
+          if (__float_as_uint(d[t][r]) != want) fail |= 1u << t;
+        }
+    }
+
+    // LDS: permuted write, barrier, read back words another wave wrote
+    const uint32_t seed =
+        (uint32_t)rep * 0x9E3779B9u + (uint32_t)blockIdx.x * 0x85EBCA6Bu;
+#pragma unroll 4
+    for (int i = tid; i < kCovLdsWords; i += kCovBlock)
+      lds[(i * 5 + 7) & (kCovLdsWords - 1)] = ((uint32_t)i * 2654435761u) ^ seed;
+    __syncthreads();
+#pragma unroll 4
+    for (int i = tid; i < kCovLdsWords; i += kCovBlock) {
+      const int j = kCovLdsWords - 1 - i;  // written by thread 255 - tid
+      const uint32_t want = (((uint32_t)j * 2654435761u) ^ seed) ^ px_lds;
+      if (lds[(j * 5 + 7) & (kCovLdsWords - 1)] != want) fail |= kCovFailLds;
+    }
+    __syncthreads();
+  }
+
+  // wave-wide OR of the per-lane masks, then one lane records the wave
+  unsigned wave_fail = 0;
+  for (int b = 0; b < 4; ++b)
+    if (__ballot((fail >> b) & 1u) != 0) wave_fail |= 1u << b;
+  if (lane == 0) {
+    const uint32_t slot = key * 4u + simd;  // < kCovSlots by the masks above
+    atomicAdd(&slot_waves[slot], 1u);
+    if (wave_fail) atomicOr(&slot_fail[slot], wave_fail);
+    slot_hw_id[slot] = hw_id;    // raw registers, kept as evidence should the
+    slot_xcc_id[slot] = xcc_id;  // layout assumption ever fail its check
+  }
+#endif
+}
+
+// Integer operand generators: |v| <= 8, A and B unrelated (a transposed
+// fragment cannot pass), every (set, dtype) pair a different pattern.
+static int cov_a_val(int set, int dt, int m, int k) {
+  return (m * 3 + k * 5 + set * 7 + dt * 2 + (m * k) % 5) % 17 - 8;
+}
+static int cov_b_val(int set, int dt, int k, int n) {
+  return (k * 7 + n * 11 + set * 13 + dt * 4 + 3 + (k * n) % 7) % 17 - 8;
+}
+
+static uint16_t cov_to_bf16(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return (uint16_t)((u + 0x7FFF + ((u >> 16) & 1)) >> 16);
+}
+static float cov_from_bf16(uint16_t v) {
+  uint32_t u = (uint32_t)v << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+static uint32_t cov_f32_bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
+
+// One (set, dtype) problem: encoded operands, their decoded f32 values and
+// the expected tile, which is computed in integers from the intended values
+// (not from the decoded ones, so an encoding that fails to round-trip shows).
+struct CovProblem {
+  int k;
+  std::vector<uint32_t> a_enc, b_enc;  // f32 bits / bf16 / e4m3 code per element
+  std::vector<float> a_dec, b_dec, d;  // row-major 16xK, Kx16, 16x16
+};
+
+static const char* const kCovDtypeNames[3] = {"f32", "bf16", "fp8"};
+
+static CovProblem cov_problem(int set, int dt) {
+  CovProblem p;
+  p.k = dt == 0 ? 4 : 32;
+  const int K = p.k;
+  std::vector<int> a(16 * K), b(K * 16);
+  for (int m = 0; m < 16; ++m)
+    for (int k = 0; k < K; ++k) a[m * K + k] = cov_a_val(set, dt, m, k);
+  for (int k = 0; k < K; ++k)
+    for (int n = 0; n < 16; ++n) b[k * 16 + n] = cov_b_val(set, dt, k, n);
+  auto encode = [dt](int v, uint32_t* enc, float* dec) {
+    const float f = (float)v;
+    if (dt == 0) {
+      *enc = cov_f32_bits(f);
+      *dec = f;
+    } else if (dt == 1) {
+      const uint16_t h = cov_to_bf16(f);
+      *enc = h;
+      *dec = cov_from_bf16(h);
+    } else {
+      const uint8_t q = encode_e4m3fn_nearest(f);
+      *enc = q;
+      *dec = decode_e4m3fn(q);
+    }
+  };
+  p.a_enc.resize(16 * K);
+  p.a_dec.resize(16 * K);
+  p.b_enc.resize(K * 16);
+  p.b_dec.resize(K * 16);
+  for (int i = 0; i < 16 * K; ++i) encode(a[i], &p.a_enc[i], &p.a_dec[i]);
+  for (int i = 0; i < K * 16; ++i) encode(b[i], &p.b_enc[i], &p.b_dec[i]);
+  p.d.resize(256);
+  for (int m = 0; m < 16; ++m)
+    for (int n = 0; n < 16; ++n) {
+      int acc = 0;
+      for (int k = 0; k < K; ++k) acc += a[m * K + k] * b[k * 16 + n];
+      p.d[m * 16 + n] = (float)acc;
+    }
+  return p;
+}
+
+// Pack every set into per-lane fragment records for the kernel.
+static std::vector<uint32_t> cov_build_table() {
+  std::vector<uint32_t> tab((size_t)kCovSets * 64 * kCovRecWords, 0u);
+  for (int s = 0; s < kCovSets; ++s) {
+    CovProblem pr[3] = {cov_problem(s, 0), cov_problem(s, 1), cov_problem(s, 2)};
+    for (int l = 0; l < 64; ++l) {
+      CovLaneRec rec;
+      std::memset(&rec, 0, sizeof(rec));
+      const int lo = l & 15, hi = l >> 4;
+      rec.f32_a = pr[0].a_enc[lo * 4 + hi];
+      rec.f32_b = pr[0].b_enc[hi * 16 + lo];
+      for (int i = 0; i < 8; ++i) {
+        const int k = hi * 8 + i;
+        rec.bf16_a[i / 2] |= pr[1].a_enc[lo * 32 + k] << (16 * (i & 1));
+        rec.bf16_b[i / 2] |= pr[1].b_enc[k * 16 + lo] << (16 * (i & 1));
+        rec.fp8_a[i / 4] |= pr[2].a_enc[lo * 32 + k] << (8 * (i & 3));
+        rec.fp8_b[i / 4] |= pr[2].b_enc[k * 16 + lo] << (8 * (i & 3));
+      }
+      for (int t = 0; t < 3; ++t)
+        for (int r = 0; r < 4; ++r)
+          rec.exp[t][r] = cov_f32_bits(pr[t].d[(hi * 4 + r) * 16 + lo]);
+      std::memcpy(&tab[(size_t)(s * 64 + l) * kCovRecWords], &rec, sizeof(rec));
+    }
+  }
+  return tab;
+}
+
+static py::dict cu_coverage_reference() {
+  // host only: no HIP call
+  py::dict out;
+  out["sets"] = kCovSets;
+  out["m"] = 16;
+  out["n"] = 16;
+  for (int t = 0; t < 3; ++t) {
+    py::list per_set;
+    for (int s = 0; s < kCovSets; ++s) {
+      CovProblem p = cov_problem(s, t);
+      py::dict e;
+      e["k"] = p.k;
+      e["a"] = p.a_dec;  // decoded from the encoded operand, row-major 16xK
+      e["b"] = p.b_dec;  // row-major Kx16
+      e["d"] = p.d;      // expected tile, row-major 16x16
+      per_set.append(e);
+    }
+    out[kCovDtypeNames[t]] = per_set;
+  }
+  return out;
+}
+
+// RAII holders local to the sweep: nothing leaks when HIP_CHECK throws.
+struct CovDeviceBuf {
+  void* ptr = nullptr;
+  CovDeviceBuf() = default;
+  CovDeviceBuf(const CovDeviceBuf&) = delete;
+  CovDeviceBuf& operator=(const CovDeviceBuf&) = delete;
+  ~CovDeviceBuf() {
+    if (ptr) (void)hipFree(ptr);
+  }
+  void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&ptr, bytes)); }
+  uint32_t* u32() const { return static_cast<uint32_t*>(ptr); }
+};
+
+struct CovEvent {
+  hipEvent_t ev = nullptr;
+  CovEvent() = default;
+  CovEvent(const CovEvent&) = delete;
+  CovEvent& operator=(const CovEvent&) = delete;
+  ~CovEvent() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  void create() { HIP_CHECK(hipEventCreate(&ev)); }
+};
+
+static py::dict cu_coverage_check(int device, int reps, int max_rounds,
+                                  int poison_key, unsigned poison_mask,
+                                  bool poison_all) {
+  if (reps < 1 || reps > 4096)
+    throw std::invalid_argument("cu_coverage_check: reps must be in [1, 4096]");
+  if (max_rounds < 1 || max_rounds > 64)
+    throw std::invalid_argument("cu_coverage_check: max_rounds must be in [1, 64]");
+  if (poison_key < -1 || poison_key >= kCovKeys)
+    throw std::invalid_argument("cu_coverage_check: poison_key out of range");
+  if (poison_mask > 0xFu)
+    throw std::invalid_argument("cu_coverage_check: poison_mask has 4 bits");
+
+  hipDeviceProp_t prop;
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipGetDeviceProperties(&prop, device));
+  const int cus = prop.multiProcessorCount;
+  if (cus < 1 || cus > kCovKeys)
+    throw std::runtime_error("cu_coverage_check: implausible compute unit count");
+  if (prop.sharedMemPerBlock < sizeof(uint32_t) * kCovLdsWords)
+    throw std::runtime_error(
+        "cu_coverage_check: device grants less than 64 KiB of LDS per workgroup");
+
+  const std::vector<uint32_t> tab = cov_build_table();
+  const size_t slot_bytes = sizeof(uint32_t) * kCovSlots;
+  CovDeviceBuf d_tab, d_slots;  // d_slots: waves | fail | hw_id | xcc_id
+  d_tab.alloc(sizeof(uint32_t) * tab.size());
+  d_slots.alloc(4 * slot_bytes);
+  HIP_CHECK(hipMemcpy(d_tab.ptr, tab.data(), sizeof(uint32_t) * tab.size(),
+                      hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_slots.ptr, 0, 4 * slot_bytes));
+  CovEvent t0, t1;
+  t0.create();
+  t1.create();
+
+  std::vector<uint32_t> h((size_t)4 * kCovSlots);
+  const uint32_t* h_waves = h.data();
+  const uint32_t* h_fail = h.data() + kCovSlots;
+  const uint32_t* h_hw = h.data() + 2 * kCovSlots;
+  const uint32_t* h_xcc = h.data() + 3 * kCovSlots;
+  int rounds = 0, cus_covered = 0, slots_covered = 0;
+  double elapsed_ms = 0.0;
+  while (rounds < max_rounds) {
+    HIP_CHECK(hipEventRecord(t0.ev));
+    hipLaunchKernelGGL(cu_coverage_kernel, dim3(kCovBlocksPerCu * cus),
+                       dim3(kCovBlock), 0, 0, d_tab.u32(), d_slots.u32(),
+                       d_slots.u32() + kCovSlots, d_slots.u32() + 2 * kCovSlots,
+                       d_slots.u32() + 3 * kCovSlots, reps, poison_key,
+                       poison_mask, poison_all ? 1 : 0);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(t1.ev));
+    HIP_CHECK(hipEventSynchronize(t1.ev));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+    elapsed_ms += ms;
+    ++rounds;
+    HIP_CHECK(hipMemcpy(h.data(), d_slots.ptr, 4 * slot_bytes,
+                        hipMemcpyDeviceToHost));
+    cus_covered = slots_covered = 0;
+    for (int key = 0; key < kCovKeys; ++key) {
+      int simds = 0;
+      for (int s = 0; s < 4; ++s) simds += h_waves[key * 4 + s] != 0;
+      cus_covered += simds != 0;
+      slots_covered += simds;
+    }
+    if (cus_covered >= cus && slots_covered >= 4 * cus) break;
+  }
+
+  py::list units;
+  long waves_run = 0;
+  int failed_slots = 0;
+  for (int slot = 0; slot < kCovSlots; ++slot) {
+    if (h_waves[slot] == 0) continue;
+    const int key = slot >> 2;
+    py::dict u;
+    u["key"] = key;
+    u["xcc"] = key >> 8;
+    u["hw_bits"] = key & 0xFF;
+    u["simd"] = slot & 3;
+    u["waves"] = h_waves[slot];
+    u["fail_mask"] = h_fail[slot];
+    u["hw_id_raw"] = h_hw[slot];
+    u["xcc_id_raw"] = h_xcc[slot];
+    units.append(u);
+    waves_run += h_waves[slot];
+    failed_slots += h_fail[slot] != 0;
+  }
+  py::dict out;
+  out["compute_units"] = cus;
+  out["cus_covered"] = cus_covered;
+  out["simd_slots_covered"] = slots_covered;
+  out["waves_run"] = waves_run;
+  out["rounds"] = rounds;
+  out["failed_slots"] = failed_slots;
+  out["units"] = units;
+  out["elapsed_ms"] = elapsed_ms;
+  return out;
+}
+
 PYBIND11_MODULE(_gpu_validator, m) {
   m.doc() = "MI355X (gfx950) native GPU health validator";
+  m.def("cu_coverage_check", &cu_coverage_check, py::arg("device") = 0,
+        py::arg("reps") = 32, py::arg("max_rounds") = 8,
+        py::arg("poison_key") = -1, py::arg("poison_mask") = 0u,
+        py::arg("poison_all") = false,
+        "Whole-device sweep: f32/bf16/fp8 MFMA tiles + LDS round trip on every "
+        "CU and SIMD, exact comparison, results per placement key");
+  m.def("cu_coverage_reference", &cu_coverage_reference,
+        "Host-only: the sweep's operand sets (decoded to f32) and expected "
+        "tiles per dtype");
   m.def("device_probe", &device_probe, py::arg("device") = 0);
   m.def("mfma_f32_check", &mfma_f32_check, py::arg("device") = 0,
         "Max abs error of a v_mfma_f32_16x16x4_f32 tile vs exact CPU fmaf chain");

@@ -12,7 +12,10 @@ Layers:
 - the native ``_gpu_validator`` HIP extension — device probe, MFMA matrix
   core smoke tests (f32-exact and bf16), HBM streaming bandwidth, LDS
   integrity.  **Fails loudly if the extension is missing on a GPU machine**:
-  a silent fallback would let a broken driver pass validation.
+  a silent fallback would let a broken driver pass validation;
+- :func:`cu_coverage_check` — opt-in whole-device sweep: the f32 / bf16 / fp8
+  matrix paths and LDS on every CU and SIMD, with failures attributed to the
+  unit that produced them (:func:`summarize_cu_coverage` is the pure verdict).
 """
 
 from .gpu_health import (  # noqa: F401
@@ -20,4 +23,8 @@ from .gpu_health import (  # noqa: F401
     gpu_health_check,
     load_native_validator,
     smi_probe,
+)
+from .cu_coverage import (  # noqa: F401
+    cu_coverage_check,
+    summarize_cu_coverage,
 )

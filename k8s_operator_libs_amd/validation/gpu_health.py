@@ -87,10 +87,13 @@ def gpu_health_check(
     bw_iters: int = 5,
     require_gpu: bool = False,
     deep: bool = False,
+    coverage: bool = False,
 ) -> Dict[str, Any]:
     """Full node GPU health check.  Returns a report dict with a top-level
     ``healthy`` verdict; raises GpuHealthError when ``require_gpu`` and no
-    usable GPU/native validator is present."""
+    usable GPU/native validator is present.  ``coverage`` adds the
+    whole-device per-CU sweep (see :mod:`.cu_coverage`) and gates the verdict
+    on it."""
     report: Dict[str, Any] = {"healthy": False, "checks": {}}
     report["checks"]["smi"] = smi_probe()
 
@@ -126,6 +129,15 @@ def gpu_health_check(
         report["checks"]["mfma_throughput_tflops"] = tflops
         deep_ok = fp8_err <= MFMA_FP8_MAX_ERR and tflops >= MFMA_MIN_TFLOPS
 
+    coverage_ok = True
+    if coverage:
+        # opt-in: MFMA + LDS on every CU and SIMD, attributed per unit
+        from .cu_coverage import summarize_cu_coverage
+
+        summary = summarize_cu_coverage(native.cu_coverage_check(device))
+        report["checks"]["cu_coverage"] = summary
+        coverage_ok = summary["healthy"]
+
     # multi-GPU nodes: verify every xGMI peer link is up
     xgmi_ok = True
     if probe.get("device_count", 1) > 1:
@@ -142,16 +154,21 @@ def gpu_health_check(
         and lds_ok
         and xgmi_ok
         and deep_ok
+        and coverage_ok
     )
     return report
 
 
 def main() -> int:
     """CLI entry point for use inside a validation pod.  Pass ``--deep`` for
-    the fp8 + burn-in checks."""
+    the fp8 + burn-in checks and ``--coverage`` for the per-CU sweep."""
     import sys
 
-    report = gpu_health_check(require_gpu=True, deep="--deep" in sys.argv)
+    report = gpu_health_check(
+        require_gpu=True,
+        deep="--deep" in sys.argv,
+        coverage="--coverage" in sys.argv,
+    )
     print(json.dumps(report, indent=2, default=str))  # noqa: T201 (CLI/build output)
     return 0 if report["healthy"] else 1
 
