@@ -69,5 +69,7 @@ coverage:
 		|| $(PY) -m pytest tests/ -q -m "not gpu" --timeout 300
 
 clean:
-	rm -f k8s_operator_libs_amd/native/_gpu_validator.so
+	rm -f k8s_operator_libs_amd/native/_gpu_validator.so \
+		k8s_operator_libs_amd/native/_jsonops.so \
+		k8s_operator_libs_amd/native/_wire.so
 	find . -name __pycache__ -type d -exec rm -rf {} + 2>/dev/null || true

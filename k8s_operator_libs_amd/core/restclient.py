@@ -24,6 +24,7 @@ from typing import Any, Dict, Optional
 
 import httpx
 
+from ..native import load_wire as _load_wire
 from . import meta
 from .client import Client
 from .errors import (
@@ -90,12 +91,16 @@ class RestClient(Client):
         # stack — and request latency IS the reconcile loop's wire cost.
         # TLS endpoints (real apiservers) stay on httpx.
         self._fast_netloc = None
+        self._wire = None
         if self.base_url.startswith("http://"):
             import urllib.parse
 
             parsed = urllib.parse.urlsplit(self.base_url)
             self._fast_netloc = (parsed.hostname, parsed.port or 80)
             self._fast_local = __import__("threading").local()
+            # native wire path (plain HTTP only; TLS never takes it)
+            self._wire = _load_wire()
+            self._wire_heads: Dict[tuple, bytes] = {}
         self._kinds = dict(_KIND_INFO)
         if extra_kinds:
             self._kinds.update(extra_kinds)
@@ -103,8 +108,94 @@ class RestClient(Client):
 
     # -- plain-HTTP fast transport -------------------------------------------
 
+    def _wire_head(self, headers=None) -> bytes:
+        """The request's header block (Host, auth, content type), encoded
+        once per client and per distinct override rather than per request."""
+        key = tuple(sorted(headers.items())) if headers else ()
+        head = self._wire_heads.get(key)
+        if head is None:
+            host, port = self._fast_netloc
+            if ":" in host:
+                host = f"[{host}]"
+            hdrs = {"Host": host if port == 80 else f"{host}:{port}",
+                    "Accept-Encoding": "identity"}
+            hdrs.update(self._headers)
+            if headers:
+                hdrs.update(headers)
+            head = "".join(f"{k}: {v}\r\n" for k, v in hdrs.items()).encode(
+                "latin-1")
+            self._wire_heads[key] = head
+        return head
+
+    def _wire_connect(self):
+        import socket
+
+        sock = socket.create_connection(self._fast_netloc,
+                                        timeout=self._timeout)
+        sock.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
+        return sock
+
+    def _wire_request(self, method: str, path: str, params=None, content=None,
+                      headers=None):
+        """``_fast_request`` over the native extension: one send, then
+        poll/recv with the GIL released and no Python-level parsing.  The
+        thread-local socket stays owned here; the extension only borrows
+        its fd.  Same reconnect-once behaviour as the http.client path."""
+        import urllib.parse
+
+        if params:
+            path = f"{path}?{urllib.parse.urlencode(params)}"
+        head = self._wire_head(headers)
+        sock = getattr(self._fast_local, "sock", None)
+        for attempt in (0, 1):
+            try:
+                if sock is None:
+                    sock = self._wire_connect()
+                    self._fast_local.sock = sock
+                status, data, reusable = self._wire.exchange(
+                    sock.fileno(), method, path, head, content, self._timeout)
+            except ValueError as exc:
+                # malformed framing: the connection is unusable and the
+                # request is not resent; surface it as the protocol error
+                # the retry loop in _request already understands
+                self._wire_drop(sock)
+                raise _http_client.HTTPException(str(exc)) from exc
+            except (ConnectionError, OSError):
+                # keep-alive connection died (server restart/idle close):
+                # reconnect once, then let the caller's retry logic own it.
+                # On purpose exactly what the http.client path below does,
+                # no wider: OSError covers TimeoutError, so a request that
+                # timed out after it was sent is resent once there too
+                # (ADVICE.md flags that resend; narrowing it is a change of
+                # its own, for both paths at once).
+                self._wire_drop(sock)
+                sock = None
+                if attempt:
+                    raise
+            except BaseException:
+                # interrupted mid-exchange (Ctrl-C): a half-read response
+                # must not be left for the next request
+                self._wire_drop(sock)
+                raise
+            else:
+                if not reusable:
+                    self._wire_drop(sock)
+                return _FastResponse(status, data)
+        raise AssertionError("unreachable")
+
+    def _wire_drop(self, sock) -> None:
+        if sock is not None:
+            try:
+                sock.close()
+            except Exception:
+                pass
+        self._fast_local.sock = None
+
     def _fast_request(self, method: str, path: str, params=None, content=None,
                       headers=None):
+        if self._wire is not None:
+            return self._wire_request(method, path, params=params,
+                                      content=content, headers=headers)
         import http.client
         import urllib.parse
 
@@ -414,6 +505,7 @@ class RestClient(Client):
                 except Exception:
                     pass
                 self._fast_local.conn = None
+            self._wire_drop(getattr(self._fast_local, "sock", None))
 
 
 class _FastResponse:
@@ -509,6 +601,68 @@ class _HttpWatch:
             finally:
                 self._connected.set()  # never leave a waiter hanging
 
+        def native_reader():
+            # plain-HTTP endpoints: own socket, head and line framing parsed
+            # natively with the GIL released while waiting
+            import urllib.parse
+
+            wire = client._wire
+            sock = None
+            try:
+                sock = client._wire_connect()
+                self._sock = sock  # stop() shuts it down to unblock instantly
+                if self._stop.is_set():
+                    return
+                request = (
+                    f"GET {path}?{urllib.parse.urlencode(params)} HTTP/1.1\r\n"
+                ).encode("latin-1") + client._wire_head() + b"\r\n"
+                sock.sendall(request)
+                lines = wire.LineReader(sock.fileno())
+                status = lines.read_head(client._timeout)
+                if status == 410:
+                    from .errors import GoneError
+
+                    self._error = GoneError("watch resume point expired")
+                    return
+                if status >= 400:
+                    err = ApiError(f"watch rejected: HTTP {status}")
+                    err.code = status
+                    self._error = err
+                    return
+                # headers received: the server has registered the watch
+                self._connected.set()
+                while not self._stop.is_set():
+                    try:
+                        line = lines.readline(None)
+                    except EOFError:
+                        break
+                    if line is None:
+                        continue
+                    try:
+                        event = json.loads(line)
+                    except ValueError:
+                        continue
+                    self._queue.put((event.get("type"), event.get("object")))
+            except Exception as exc:
+                if not self._stop.is_set():
+                    import logging as _logging
+
+                    _logging.getLogger(__name__).warning(
+                        "watch stream ended: %s", exc
+                    )
+            finally:
+                self._connected.set()  # never leave a waiter hanging
+                # closed only here, after readline has returned: the fd
+                # cannot be reused under a blocked recv
+                if sock is not None:
+                    try:
+                        sock.close()
+                    except Exception:
+                        pass
+
+        self._sock = None
+        if client._wire is not None and client._fast_netloc is not None:
+            reader = native_reader
         self._resp = None
         self._thread = threading.Thread(target=reader, daemon=True)
         self._thread.start()
@@ -526,6 +680,16 @@ class _HttpWatch:
 
     def stop(self) -> None:
         self._stop.set()
+        sock = self._sock
+        if sock is not None:
+            # wake the native reader; it closes the socket itself once it
+            # has left readline
+            import socket
+
+            try:
+                sock.shutdown(socket.SHUT_RDWR)
+            except OSError:
+                pass
         resp = self._resp
         if resp is not None:
             # close the stream so the blocked reader exits immediately

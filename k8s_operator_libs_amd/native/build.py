@@ -16,6 +16,11 @@ SOURCE = os.path.join(PKG_DIR, "gpu_validator.hip")
 OUTPUT = os.path.join(PKG_DIR, "_gpu_validator.so")
 JSONOPS_SOURCE = os.path.join(PKG_DIR, "jsonops.cpp")
 JSONOPS_OUTPUT = os.path.join(PKG_DIR, "_jsonops.so")
+WIRE_SOURCES = (
+    os.path.join(PKG_DIR, "wire.cpp"),
+    os.path.join(PKG_DIR, "wire_core.hpp"),
+)
+WIRE_OUTPUT = os.path.join(PKG_DIR, "_wire.so")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
@@ -44,10 +49,32 @@ def build_jsonops(force: bool = False, verbose: bool = False) -> str:
     return JSONOPS_OUTPUT
 
 
+def build_wire(force: bool = False, verbose: bool = False) -> str:
+    """Compile the native HTTP/1.1 wire path (plain C++, no ROCm); stale
+    when either wire.cpp or wire_core.hpp is newer than the .so."""
+    if (
+        not force
+        and os.path.exists(WIRE_OUTPUT)
+        and all(os.path.getmtime(WIRE_OUTPUT) >= os.path.getmtime(src)
+                for src in WIRE_SOURCES)
+    ):
+        return WIRE_OUTPUT
+    cmd = [
+        CXX, "-O3", "-std=c++17", "-fPIC", "-shared",
+        f"-I{sysconfig.get_paths()['include']}",
+        WIRE_SOURCES[0], "-o", WIRE_OUTPUT,
+    ]
+    if verbose:
+        print(" ".join(cmd))  # noqa: T201 (CLI/build output)
+    subprocess.run(cmd, check=True, capture_output=not verbose)
+    return WIRE_OUTPUT
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile gpu_validator.hip -> _gpu_validator.so for gfx950 (and the
-    plain-C++ _jsonops accelerator)."""
+    plain-C++ _jsonops and _wire accelerators)."""
     build_jsonops(force=force, verbose=verbose)
+    build_wire(force=force, verbose=verbose)
     if is_built() and not force:
         return OUTPUT
     import pybind11
