@@ -19,6 +19,8 @@
 //   xgmi_p2p_probe()      — peer reachability + p2p bandwidth per xGMI link
 //   cu_coverage_check()   — f32/bf16/fp8 MFMA + LDS on every CU and SIMD,
 //                           exact, attributed per unit (opt-in sweep)
+//   hbm_pattern_check()   — moving-inversions pattern test over a region of
+//                           HBM, exact, failing words recorded (opt-in)
 //
 // Built standalone with hipcc (no torch linkage) via pybind11; the .so lives
 // in-tree so it travels to GPU nodes with the package.
@@ -961,8 +963,455 @@ static py::dict cu_coverage_check(int device, int reps, int max_rounds,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// HBM data-integrity check: a moving-inversions pattern test over a region of
+// device memory that is allocated in chunks.  Every pattern runs three phases
+// over the whole region (all chunks) before the next phase starts:
+//   fill           write p
+//   verify_invert  read, compare with p, write ~p to the same address
+//   verify         read, compare with ~p
+// so that for a region larger than the caches each read is served by HBM.
+// The written ~p is computed from the pattern, never from the data read.
+//
+// A pattern is a pure function of the region's logical 64-bit word index, so
+// an aliased or mis-decoded address reads back another index's word:
+//   hash     splitmix64 finaliser of (i + seed * golden ratio): every data
+//            bit toggles, no two nearby or power-of-two-distant words agree
+//   checker  0xAAAA.. for even i, 0x5555.. for odd i (seed ignored)
+//
+// Comparison is exact.  A lane counts the words it compared; each workgroup
+// adds its total to one of kHbmShards counters once, at its end, and the host
+// checks coverage by summing them (counted, not trusted).  Only a mismatching
+// lane touches the error counter, the xor mask and the capped record buffer.
+// Every kernel does a fixed amount of work and exits: no spins, no waits
+// between workgroups.
+//
+// The poison hook is data only: it XORs a mask into the *expected* value of
+// the selected words and never alters memory, so a record's `got` is what the
+// fill kernel really wrote.
+// ---------------------------------------------------------------------------
+
+constexpr int kHbmPatternHash = 0, kHbmPatternChecker = 1;
+constexpr int kHbmFill = 0, kHbmVerifyInvert = 1, kHbmVerify = 2;
+constexpr int kHbmBlock = 512;            // bw_copy_kernel's sweep-tuned shape
+constexpr int kHbmShards = 1024;          // compared-word counters, one line each
+constexpr int kHbmShardStride = 16;       // in uint64: 128 bytes apart
+constexpr int kHbmMaxRecords = 4096;
+constexpr int kHbmMaxPasses = 16;
+constexpr size_t kHbmReferenceMax = 65536;
+constexpr uint64_t kHbmReserveBytes = 2ull << 30;
+constexpr uint64_t kHbmBeyondCacheBytes = 512ull << 20;  // 2 x Infinity Cache
+
+// The one definition shared by the kernels and the host reference.
+__host__ __device__ inline uint64_t hbm_pattern_value(int pattern, uint64_t seed,
+                                                      uint64_t i) {
+  if (pattern == kHbmPatternChecker)
+    return (i & 1ull) ? 0x5555555555555555ull : 0xAAAAAAAAAAAAAAAAull;
+  uint64_t z = i + seed * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+using u64x2 = __attribute__((ext_vector_type(2))) uint64_t;
+
+struct HbmRecord {
+  uint64_t word, phase, expected, got;
+};
+
+// Device-side result block: [0] error count, [1] xor mask, [2] record claims.
+constexpr int kHbmCtlErrors = 0, kHbmCtlXor = 1, kHbmCtlClaims = 2,
+              kHbmCtlWords = 4;
+
+struct HbmLaunch {
+  uint64_t* buf;        // this chunk
+  uint64_t nwords;      // words in this chunk
+  uint64_t base;        // logical index of the chunk's first word
+  uint64_t seed;
+  uint64_t poison_xor;
+  uint64_t poison_stride;
+  int64_t poison_word;  // -1: the hook is off for this launch
+  unsigned long long* ctl;
+  unsigned long long* shards;
+  HbmRecord* records;
+  uint32_t max_records;
+  uint32_t verify_index;
+  int pattern;
+};
+
+// test hook: data only, returns the mask to XOR into the expected value.
+// Callers test a.poison_word >= 0 first (uniform), so a normal run pays one
+// scalar branch per loop iteration and never the 64-bit modulo.
+__device__ __forceinline__ uint64_t hbm_poison(const HbmLaunch& a, uint64_t i) {
+  const uint64_t w = (uint64_t)a.poison_word;
+  if (i < w) return 0;
+  if (a.poison_stride == 0) return i == w ? a.poison_xor : 0;
+  return (i - w) % a.poison_stride == 0 ? a.poison_xor : 0;
+}
+
+// got ^ expected for word i; zero when the word is right
+__device__ __forceinline__ uint64_t hbm_diff(const HbmLaunch& a, uint64_t i,
+                                             uint64_t got, uint64_t inv) {
+  uint64_t x = got ^ hbm_pattern_value(a.pattern, a.seed, i) ^ inv;
+  if (a.poison_word >= 0) x ^= hbm_poison(a, i);
+  return x;
+}
+
+// the rare path: count the mismatch and claim a record slot
+__device__ __forceinline__ void hbm_report(const HbmLaunch& a, uint64_t i,
+                                        uint64_t got, uint64_t x, uint32_t& bad,
+                                        uint64_t& bad_xor) {
+  if (x == 0) return;
+  ++bad;
+  bad_xor |= x;
+  const unsigned long long slot = atomicAdd(&a.ctl[kHbmCtlClaims], 1ull);
+  if (slot < a.max_records) {  // claims past the cap are dropped
+    HbmRecord r = {i, a.verify_index, got ^ x, got};
+    a.records[slot] = r;
+  }
+}
+
+// kind: kHbmFill / kHbmVerifyInvert / kHbmVerify.  16-byte nontemporal
+// accesses, 2x unrolled grid-stride as in bw_copy_kernel; one thread handles
+// the odd last word of a chunk with plain scalar accesses.  The hot loop is
+// straight-line: the four differences of an iteration are ORed and only a
+// non-zero OR enters the reporting path.  A lane's counters are 32-bit: the
+// grid is never smaller than 2^19 threads.
+template <int kind>
+__global__ void __launch_bounds__(kHbmBlock) hbm_pattern_kernel(HbmLaunch a) {
+  __shared__ uint32_t wave_compared[kHbmBlock / 64];
+  u64x2* __restrict__ v = reinterpret_cast<u64x2*>(a.buf);
+  const uint64_t nvec = a.nwords >> 1;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // what a verify kernel expects to read, and what a writing kernel stores
+  const uint64_t inv = kind == kHbmVerify ? ~0ull : 0ull;
+  const uint64_t winv = kind == kHbmVerifyInvert ? ~0ull : 0ull;
+  uint32_t compared = 0, bad = 0;
+  uint64_t bad_xor = 0;
+
+  uint64_t i = tid;
+  for (; i + stride < nvec; i += 2 * stride) {
+    const uint64_t w0 = a.base + 2 * i, w1 = a.base + 2 * (i + stride);
+    if (kind != kHbmFill) {
+      const u64x2 g0 = __builtin_nontemporal_load(&v[i]);
+      const u64x2 g1 = __builtin_nontemporal_load(&v[i + stride]);
+      const uint64_t x0 = hbm_diff(a, w0, g0[0], inv);
+      const uint64_t x1 = hbm_diff(a, w0 + 1, g0[1], inv);
+      const uint64_t x2 = hbm_diff(a, w1, g1[0], inv);
+      const uint64_t x3 = hbm_diff(a, w1 + 1, g1[1], inv);
+      compared += 4;
+      if ((x0 | x1 | x2 | x3) != 0) {
+        hbm_report(a, w0, g0[0], x0, bad, bad_xor);
+        hbm_report(a, w0 + 1, g0[1], x1, bad, bad_xor);
+        hbm_report(a, w1, g1[0], x2, bad, bad_xor);
+        hbm_report(a, w1 + 1, g1[1], x3, bad, bad_xor);
+      }
+    }
+    if (kind != kHbmVerify) {
+      u64x2 p0, p1;
+      p0[0] = hbm_pattern_value(a.pattern, a.seed, w0) ^ winv;
+      p0[1] = hbm_pattern_value(a.pattern, a.seed, w0 + 1) ^ winv;
+      p1[0] = hbm_pattern_value(a.pattern, a.seed, w1) ^ winv;
+      p1[1] = hbm_pattern_value(a.pattern, a.seed, w1 + 1) ^ winv;
+      __builtin_nontemporal_store(p0, &v[i]);
+      __builtin_nontemporal_store(p1, &v[i + stride]);
+    }
+  }
+  for (; i < nvec; i += stride) {
+    const uint64_t w0 = a.base + 2 * i;
+    if (kind != kHbmFill) {
+      const u64x2 g0 = __builtin_nontemporal_load(&v[i]);
+      const uint64_t x0 = hbm_diff(a, w0, g0[0], inv);
+      const uint64_t x1 = hbm_diff(a, w0 + 1, g0[1], inv);
+      compared += 2;
+      if ((x0 | x1) != 0) {
+        hbm_report(a, w0, g0[0], x0, bad, bad_xor);
+        hbm_report(a, w0 + 1, g0[1], x1, bad, bad_xor);
+      }
+    }
+    if (kind != kHbmVerify) {
+      u64x2 p0;
+      p0[0] = hbm_pattern_value(a.pattern, a.seed, w0) ^ winv;
+      p0[1] = hbm_pattern_value(a.pattern, a.seed, w0 + 1) ^ winv;
+      __builtin_nontemporal_store(p0, &v[i]);
+    }
+  }
+  if ((a.nwords & 1ull) && tid == 0) {  // scalar tail: the odd last word
+    const uint64_t t = a.nwords - 1;
+    if (kind != kHbmFill) {
+      const uint64_t got = a.buf[t];
+      ++compared;
+      hbm_report(a, a.base + t, got, hbm_diff(a, a.base + t, got, inv), bad,
+                 bad_xor);
+    }
+    if (kind != kHbmVerify)
+      a.buf[t] = hbm_pattern_value(a.pattern, a.seed, a.base + t) ^ winv;
+  }
+
+  if (kind != kHbmFill) {
+    if (bad != 0) {  // on a mismatch, and only then
+      atomicAdd(&a.ctl[kHbmCtlErrors], (unsigned long long)bad);
+      atomicOr(&a.ctl[kHbmCtlXor], (unsigned long long)bad_xor);
+    }
+    // workgroup total of compared words -> one add to this block's shard
+    uint32_t sum = compared;
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_compared[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0;
+      for (int w = 0; w < kHbmBlock / 64; ++w) total += wave_compared[w];
+      atomicAdd(&a.shards[(blockIdx.x & (kHbmShards - 1)) * kHbmShardStride],
+                total);
+    }
+  }
+}
+
+static int hbm_pattern_id(const std::string& name) {
+  if (name == "hash") return kHbmPatternHash;
+  if (name == "checker") return kHbmPatternChecker;
+  throw std::invalid_argument("hbm pattern must be 'hash' or 'checker'");
+}
+
+static std::vector<uint64_t> hbm_pattern_reference(const std::string& pattern,
+                                                   uint64_t seed,
+                                                   uint64_t first_word,
+                                                   size_t count, bool inverted) {
+  // host only: no HIP call
+  const int id = hbm_pattern_id(pattern);
+  if (count > kHbmReferenceMax)
+    throw std::invalid_argument("hbm_pattern_reference: count is at most 65536");
+  std::vector<uint64_t> out(count);
+  for (size_t k = 0; k < count; ++k) {
+    const uint64_t v = hbm_pattern_value(id, seed, first_word + k);
+    out[k] = inverted ? ~v : v;
+  }
+  return out;
+}
+
+// RAII holders in the style of CovDeviceBuf / CovEvent.
+struct HbmDeviceBuf {
+  void* ptr = nullptr;
+  HbmDeviceBuf() = default;
+  HbmDeviceBuf(const HbmDeviceBuf&) = delete;
+  HbmDeviceBuf& operator=(const HbmDeviceBuf&) = delete;
+  HbmDeviceBuf(HbmDeviceBuf&& o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
+  ~HbmDeviceBuf() {
+    if (ptr) (void)hipFree(ptr);
+  }
+  void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&ptr, bytes)); }
+};
+
+struct HbmChunk {
+  HbmDeviceBuf buf;
+  uint64_t first_word = 0;  // logical
+  uint64_t words = 0;
+};
+
+static void hbm_launch(int kind, const HbmLaunch& a) {
+  // bw_copy_kernel's launch shape: ~2 vectors per thread, grid in [1024, 131072]
+  const uint64_t nvec = a.nwords >> 1;
+  const long want = (long)(nvec / (2 * (uint64_t)kHbmBlock)) + 1;
+  const int grid = (int)std::min<long>(131072, std::max<long>(1024, want));
+  if (kind == kHbmFill)
+    hipLaunchKernelGGL(hbm_pattern_kernel<kHbmFill>, dim3(grid), dim3(kHbmBlock),
+                       0, 0, a);
+  else if (kind == kHbmVerifyInvert)
+    hipLaunchKernelGGL(hbm_pattern_kernel<kHbmVerifyInvert>, dim3(grid),
+                       dim3(kHbmBlock), 0, 0, a);
+  else
+    hipLaunchKernelGGL(hbm_pattern_kernel<kHbmVerify>, dim3(grid),
+                       dim3(kHbmBlock), 0, 0, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+static py::dict hbm_pattern_check(int device, uint64_t nbytes,
+                                  uint64_t chunk_bytes, int passes,
+                                  uint64_t seed, bool checker,
+                                  uint64_t first_word, int max_records,
+                                  int64_t poison_word, uint64_t poison_stride,
+                                  uint64_t poison_xor, int poison_phase) {
+  // every argument is validated before the first HIP call
+  if (nbytes % 8 != 0)
+    throw std::invalid_argument("hbm_pattern_check: nbytes must be a multiple of 8");
+  if (chunk_bytes == 0 || chunk_bytes % 8 != 0)
+    throw std::invalid_argument(
+        "hbm_pattern_check: chunk_bytes must be a positive multiple of 8");
+  if (passes < 1 || passes > kHbmMaxPasses)
+    throw std::invalid_argument("hbm_pattern_check: passes must be in [1, 16]");
+  if (max_records < 1 || max_records > kHbmMaxRecords)
+    throw std::invalid_argument("hbm_pattern_check: max_records must be in [1, 4096]");
+  if (first_word > (1ull << 62) || nbytes > (1ull << 62))
+    throw std::invalid_argument("hbm_pattern_check: region out of the index range");
+  const int n_patterns = passes + (checker ? 1 : 0);
+  const int n_verify = 2 * n_patterns;
+  if (poison_word < -1)
+    throw std::invalid_argument("hbm_pattern_check: poison_word is -1 or an index");
+  if (poison_word >= 0 && poison_xor == 0)
+    throw std::invalid_argument(
+        "hbm_pattern_check: poison_xor must be non-zero with a poison_word");
+  if (poison_phase < -1 || poison_phase >= n_verify)
+    throw std::invalid_argument("hbm_pattern_check: poison_phase out of range");
+
+  HIP_CHECK(hipSetDevice(device));
+  size_t free_b = 0, total_b = 0;
+  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  const uint64_t usable =
+      free_b > kHbmReserveBytes ? (uint64_t)free_b - kHbmReserveBytes : 0;
+  if (nbytes == 0) {
+    nbytes = usable & ~7ull;
+    if (nbytes == 0)
+      throw std::runtime_error(
+          "hbm_pattern_check: no free device memory beyond the 2 GiB reserve");
+  } else if (nbytes > usable) {
+    throw std::runtime_error(
+        "hbm_pattern_check: request exceeds free device memory minus the 2 GiB "
+        "reserve (" + std::to_string(nbytes) + " > " + std::to_string(usable) + ")");
+  }
+  const uint64_t words = nbytes / 8;
+  const uint64_t chunk_words = chunk_bytes / 8;
+
+  // a chunk that cannot be allocated raises: never silently test less
+  std::vector<HbmChunk> chunks;
+  chunks.reserve((size_t)((words + chunk_words - 1) / chunk_words));
+  for (uint64_t off = 0; off < words; off += chunk_words) {
+    chunks.emplace_back();
+    HbmChunk& c = chunks.back();
+    c.first_word = first_word + off;
+    c.words = std::min(chunk_words, words - off);
+    c.buf.alloc((size_t)(c.words * 8));
+  }
+
+  HbmDeviceBuf d_ctl, d_shards, d_records;
+  const size_t shard_bytes = sizeof(uint64_t) * kHbmShards * kHbmShardStride;
+  d_ctl.alloc(sizeof(uint64_t) * kHbmCtlWords);
+  d_shards.alloc(shard_bytes);
+  d_records.alloc(sizeof(HbmRecord) * (size_t)max_records);
+  HIP_CHECK(hipMemset(d_ctl.ptr, 0, sizeof(uint64_t) * kHbmCtlWords));
+  HIP_CHECK(hipMemset(d_shards.ptr, 0, shard_bytes));
+  HIP_CHECK(hipMemset(d_records.ptr, 0, sizeof(HbmRecord) * (size_t)max_records));
+  CovEvent t0, t1;
+  t0.create();
+  t1.create();
+
+  static const char* const kKindNames[3] = {"fill", "verify_invert", "verify"};
+  py::list phases;
+  double elapsed_ms = 0.0;
+  int phase_index = 0, verify_index = 0;
+  for (int p = 0; p < n_patterns; ++p) {
+    const bool is_hash = p < passes;
+    const uint64_t pseed = is_hash ? seed + (uint64_t)p : 0;
+    for (int kind = kHbmFill; kind <= kHbmVerify; ++kind) {
+      const bool verifies = kind != kHbmFill;
+      const bool poisoned = verifies && poison_word >= 0 &&
+                            (poison_phase < 0 || poison_phase == verify_index);
+      HIP_CHECK(hipEventRecord(t0.ev));
+      for (const HbmChunk& c : chunks) {
+        HbmLaunch a;
+        a.buf = static_cast<uint64_t*>(c.buf.ptr);
+        a.nwords = c.words;
+        a.base = c.first_word;
+        a.seed = pseed;
+        a.poison_xor = poison_xor;
+        a.poison_stride = poison_stride;
+        a.poison_word = poisoned ? poison_word : -1;
+        a.ctl = static_cast<unsigned long long*>(d_ctl.ptr);
+        a.shards = static_cast<unsigned long long*>(d_shards.ptr);
+        a.records = static_cast<HbmRecord*>(d_records.ptr);
+        a.max_records = (uint32_t)max_records;
+        a.verify_index = (uint32_t)verify_index;
+        a.pattern = is_hash ? kHbmPatternHash : kHbmPatternChecker;
+        hbm_launch(kind, a);
+      }
+      HIP_CHECK(hipEventRecord(t1.ev));
+      HIP_CHECK(hipEventSynchronize(t1.ev));
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+      elapsed_ms += ms;
+      // bytes the phase really moves: verify_invert reads and writes
+      const double moved = (kind == kHbmVerifyInvert ? 2.0 : 1.0) * (double)nbytes;
+      py::dict ph;
+      ph["index"] = phase_index++;
+      ph["pattern"] = is_hash ? "hash" : "checker";
+      ph["seed"] = pseed;
+      ph["kind"] = kKindNames[kind];
+      if (verifies)
+        ph["verify_index"] = verify_index++;
+      else
+        ph["verify_index"] = py::none();
+      ph["ms"] = (double)ms;
+      ph["gbps"] = ms > 0.f ? moved / 1e9 / ((double)ms / 1e3) : 0.0;
+      phases.append(ph);
+    }
+  }
+
+  uint64_t ctl[kHbmCtlWords];
+  std::vector<uint64_t> shards((size_t)kHbmShards * kHbmShardStride);
+  HIP_CHECK(hipMemcpy(ctl, d_ctl.ptr, sizeof(ctl), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(shards.data(), d_shards.ptr, shard_bytes,
+                      hipMemcpyDeviceToHost));
+  const uint64_t claims = ctl[kHbmCtlClaims];
+  const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)max_records);
+  std::vector<HbmRecord> recs(kept);
+  if (kept)
+    HIP_CHECK(hipMemcpy(recs.data(), d_records.ptr, sizeof(HbmRecord) * kept,
+                        hipMemcpyDeviceToHost));
+  uint64_t words_verified = 0;
+  for (int s = 0; s < kHbmShards; ++s)
+    words_verified += shards[(size_t)s * kHbmShardStride];
+
+  py::list chunk_list;
+  for (size_t c = 0; c < chunks.size(); ++c) {
+    py::dict e;
+    e["index"] = c;
+    e["first_word"] = chunks[c].first_word;
+    e["bytes"] = chunks[c].words * 8;
+    chunk_list.append(e);
+  }
+  py::list records;
+  for (const HbmRecord& r : recs) {
+    py::dict e;
+    e["word"] = r.word;
+    e["byte_offset"] = 8 * (r.word - first_word);
+    e["chunk"] = (r.word - first_word) / chunk_words;
+    e["phase"] = r.phase;
+    e["expected"] = r.expected;
+    e["got"] = r.got;
+    records.append(e);
+  }
+  py::dict out;
+  out["bytes"] = nbytes;
+  out["words"] = words;
+  out["first_word"] = first_word;
+  out["chunks"] = chunk_list;
+  out["phases"] = phases;
+  out["words_verified"] = words_verified;
+  out["words_expected"] = words * (uint64_t)n_verify;
+  out["error_count"] = ctl[kHbmCtlErrors];
+  out["xor_or"] = ctl[kHbmCtlXor];
+  out["records"] = records;
+  out["records_dropped"] = claims - (uint64_t)kept;
+  out["elapsed_ms"] = elapsed_ms;
+  out["beyond_cache"] = nbytes > kHbmBeyondCacheBytes;
+  return out;
+}
+
 PYBIND11_MODULE(_gpu_validator, m) {
   m.doc() = "MI355X (gfx950) native GPU health validator";
+  m.def("hbm_pattern_check", &hbm_pattern_check, py::arg("device") = 0,
+        py::arg("nbytes") = 1ull << 30, py::arg("chunk_bytes") = 1ull << 30,
+        py::arg("passes") = 1, py::arg("seed") = 1ull, py::arg("checker") = true,
+        py::arg("first_word") = 0ull, py::arg("max_records") = 64,
+        py::arg("poison_word") = (int64_t)-1, py::arg("poison_stride") = 0ull,
+        py::arg("poison_xor") = 0ull, py::arg("poison_phase") = -1,
+        "Moving-inversions pattern test over nbytes of device memory (0 = all "
+        "free memory minus a 2 GiB reserve), exact comparison, coverage "
+        "counted, mismatches recorded per word");
+  m.def("hbm_pattern_reference", &hbm_pattern_reference, py::arg("pattern"),
+        py::arg("seed"), py::arg("first_word"), py::arg("count"),
+        py::arg("inverted") = false,
+        "Host-only: up to 65536 expected words of a pattern from first_word");
   m.def("cu_coverage_check", &cu_coverage_check, py::arg("device") = 0,
         py::arg("reps") = 32, py::arg("max_rounds") = 8,
         py::arg("poison_key") = -1, py::arg("poison_mask") = 0u,

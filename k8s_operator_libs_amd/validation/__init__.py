@@ -15,7 +15,10 @@ Layers:
   a silent fallback would let a broken driver pass validation;
 - :func:`cu_coverage_check` — opt-in whole-device sweep: the f32 / bf16 / fp8
   matrix paths and LDS on every CU and SIMD, with failures attributed to the
-  unit that produced them (:func:`summarize_cu_coverage` is the pure verdict).
+  unit that produced them (:func:`summarize_cu_coverage` is the pure verdict);
+- :func:`hbm_integrity_check` — opt-in moving-inversions pattern test over a
+  region of HBM: exact comparison, coverage counted, failing words recorded
+  (:func:`summarize_hbm_integrity` is the pure verdict).
 """
 
 from .gpu_health import (  # noqa: F401
@@ -27,4 +30,8 @@ from .gpu_health import (  # noqa: F401
 from .cu_coverage import (  # noqa: F401
     cu_coverage_check,
     summarize_cu_coverage,
+)
+from .hbm_integrity import (  # noqa: F401
+    hbm_integrity_check,
+    summarize_hbm_integrity,
 )

@@ -88,12 +88,15 @@ def gpu_health_check(
     require_gpu: bool = False,
     deep: bool = False,
     coverage: bool = False,
+    memory: bool = False,
+    memory_mib: float = 4096.0,
 ) -> Dict[str, Any]:
     """Full node GPU health check.  Returns a report dict with a top-level
     ``healthy`` verdict; raises GpuHealthError when ``require_gpu`` and no
     usable GPU/native validator is present.  ``coverage`` adds the
     whole-device per-CU sweep (see :mod:`.cu_coverage`) and gates the verdict
-    on it."""
+    on it.  ``memory`` adds the HBM pattern test over ``memory_mib`` MiB
+    (``0``: all free memory; see :mod:`.hbm_integrity`) and gates on it too."""
     report: Dict[str, Any] = {"healthy": False, "checks": {}}
     report["checks"]["smi"] = smi_probe()
 
@@ -138,6 +141,17 @@ def gpu_health_check(
         report["checks"]["cu_coverage"] = summary
         coverage_ok = summary["healthy"]
 
+    memory_ok = True
+    if memory:
+        # opt-in: moving-inversions pattern test, summary without raw records
+        from .hbm_integrity import mib_to_bytes, summarize_hbm_integrity
+
+        mem = summarize_hbm_integrity(
+            native.hbm_pattern_check(device, mib_to_bytes(memory_mib))
+        )
+        report["checks"]["hbm_integrity"] = mem
+        memory_ok = mem["healthy"]
+
     # multi-GPU nodes: verify every xGMI peer link is up
     xgmi_ok = True
     if probe.get("device_count", 1) > 1:
@@ -155,19 +169,30 @@ def gpu_health_check(
         and xgmi_ok
         and deep_ok
         and coverage_ok
+        and memory_ok
     )
     return report
 
 
 def main() -> int:
     """CLI entry point for use inside a validation pod.  Pass ``--deep`` for
-    the fp8 + burn-in checks and ``--coverage`` for the per-CU sweep."""
+    the fp8 + burn-in checks, ``--coverage`` for the per-CU sweep and
+    ``--memory`` for the HBM pattern test (``--memory-mib=N`` sets its size
+    and implies it; ``N=0`` means all free memory)."""
     import sys
 
+    memory_kw: Dict[str, Any] = {}
+    for arg in sys.argv[1:]:
+        if arg == "--memory":
+            memory_kw["memory"] = True
+        elif arg.startswith("--memory-mib="):
+            memory_kw["memory"] = True
+            memory_kw["memory_mib"] = float(arg.split("=", 1)[1])
     report = gpu_health_check(
         require_gpu=True,
         deep="--deep" in sys.argv,
         coverage="--coverage" in sys.argv,
+        **memory_kw,
     )
     print(json.dumps(report, indent=2, default=str))  # noqa: T201 (CLI/build output)
     return 0 if report["healthy"] else 1
