@@ -21,6 +21,12 @@
 //                           exact, attributed per unit (opt-in sweep)
 //   hbm_pattern_check()   — moving-inversions pattern test over a region of
 //                           HBM, exact, failing words recorded (opt-in)
+//   mx_coverage_check()   — the MX block-scaled path (v_mfma_scale_f32_*_f8f6f4:
+//                           e4m3, e5m2, e2m3, e3m2, e2m1 with E8M0 scales, both
+//                           shapes, mixed pairs) on every CU and SIMD, exact,
+//                           attributed per unit (opt-in sweep)
+//   mx_mfma_tile()        — one scaled MFMA, raw codes + GPU tile returned
+//   mx_throughput_tflops() — sustained e2m1 / e4m3 MX burn-in
 //
 // Built standalone with hipcc (no torch linkage) via pybind11; the .so lives
 // in-tree so it travels to GPU nodes with the package.
@@ -865,29 +871,36 @@ struct CovEvent {
   void create() { HIP_CHECK(hipEventCreate(&ev)); }
 };
 
-static py::dict cu_coverage_check(int device, int reps, int max_rounds,
-                                  int poison_key, unsigned poison_mask,
-                                  bool poison_all) {
+// The host side of a whole-device sweep, shared by cu_coverage_check and
+// mx_coverage_check: argument validation before the first HIP call, table
+// upload, bounded relaunch until every CU and SIMD has been seen, and the
+// per-slot result table.  `launch(cus, tab, slots)` enqueues one round of the
+// sweep's kernel on a grid of kCovBlocksPerCu x CUs workgroups.
+template <typename Launch>
+static py::dict cov_run_sweep(const std::string& who, int device, int reps,
+                              int max_rounds, int poison_key,
+                              unsigned poison_mask, int mask_bits,
+                              const std::vector<uint32_t>& tab, Launch launch) {
   if (reps < 1 || reps > 4096)
-    throw std::invalid_argument("cu_coverage_check: reps must be in [1, 4096]");
+    throw std::invalid_argument(who + ": reps must be in [1, 4096]");
   if (max_rounds < 1 || max_rounds > 64)
-    throw std::invalid_argument("cu_coverage_check: max_rounds must be in [1, 64]");
+    throw std::invalid_argument(who + ": max_rounds must be in [1, 64]");
   if (poison_key < -1 || poison_key >= kCovKeys)
-    throw std::invalid_argument("cu_coverage_check: poison_key out of range");
-  if (poison_mask > 0xFu)
-    throw std::invalid_argument("cu_coverage_check: poison_mask has 4 bits");
+    throw std::invalid_argument(who + ": poison_key out of range");
+  if (poison_mask >= (1u << mask_bits))
+    throw std::invalid_argument(who + ": poison_mask has " +
+                                std::to_string(mask_bits) + " bits");
 
   hipDeviceProp_t prop;
   HIP_CHECK(hipSetDevice(device));
   HIP_CHECK(hipGetDeviceProperties(&prop, device));
   const int cus = prop.multiProcessorCount;
   if (cus < 1 || cus > kCovKeys)
-    throw std::runtime_error("cu_coverage_check: implausible compute unit count");
+    throw std::runtime_error(who + ": implausible compute unit count");
   if (prop.sharedMemPerBlock < sizeof(uint32_t) * kCovLdsWords)
     throw std::runtime_error(
-        "cu_coverage_check: device grants less than 64 KiB of LDS per workgroup");
+        who + ": device grants less than 64 KiB of LDS per workgroup");
 
-  const std::vector<uint32_t> tab = cov_build_table();
   const size_t slot_bytes = sizeof(uint32_t) * kCovSlots;
   CovDeviceBuf d_tab, d_slots;  // d_slots: waves | fail | hw_id | xcc_id
   d_tab.alloc(sizeof(uint32_t) * tab.size());
@@ -908,11 +921,7 @@ static py::dict cu_coverage_check(int device, int reps, int max_rounds,
   double elapsed_ms = 0.0;
   while (rounds < max_rounds) {
     HIP_CHECK(hipEventRecord(t0.ev));
-    hipLaunchKernelGGL(cu_coverage_kernel, dim3(kCovBlocksPerCu * cus),
-                       dim3(kCovBlock), 0, 0, d_tab.u32(), d_slots.u32(),
-                       d_slots.u32() + kCovSlots, d_slots.u32() + 2 * kCovSlots,
-                       d_slots.u32() + 3 * kCovSlots, reps, poison_key,
-                       poison_mask, poison_all ? 1 : 0);
+    launch(cus, d_tab.u32(), d_slots.u32());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(t1.ev));
     HIP_CHECK(hipEventSynchronize(t1.ev));
@@ -961,6 +970,727 @@ static py::dict cu_coverage_check(int device, int reps, int max_rounds,
   out["units"] = units;
   out["elapsed_ms"] = elapsed_ms;
   return out;
+}
+
+static py::dict cu_coverage_check(int device, int reps, int max_rounds,
+                                  int poison_key, unsigned poison_mask,
+                                  bool poison_all) {
+  return cov_run_sweep(
+      "cu_coverage_check", device, reps, max_rounds, poison_key, poison_mask, 4,
+      cov_build_table(), [&](int cus, uint32_t* tab, uint32_t* slots) {
+        hipLaunchKernelGGL(cu_coverage_kernel, dim3(kCovBlocksPerCu * cus),
+                           dim3(kCovBlock), 0, 0, tab, slots, slots + kCovSlots,
+                           slots + 2 * kCovSlots, slots + 3 * kCovSlots, reps,
+                           poison_key, poison_mask, poison_all ? 1 : 0);
+      });
+}
+
+// ---------------------------------------------------------------------------
+// MX block-scaled matrix path: v_mfma_scale_f32_16x16x128_f8f6f4 and
+// v_mfma_scale_f32_32x32x64_f8f6f4 with OCP MX operands (e4m3, e5m2, e2m3,
+// e3m2, e2m1) and one E8M0 scale per 32-element K block.  The 6-bit / 4-bit
+// unpackers and the scale application are hardware the bf16 / fp8 tiles never
+// touch, so they get their own exact problems, single-tile entry point,
+// whole-device sweep and burn-in.
+//
+// Format index == the instruction's cbsz / blgp code:
+//   0 e4m3   1 e5m2   2 e2m3   3 e3m2   4 e2m1
+//
+// Fragment layout, confirmed on an MI355X by the exact single-tile tests (a
+// wrong map cannot reproduce those tiles; see validation/README.md).  Lane l
+// supplies A row / B col l % M and 32 elements; with g = l / M (M = 16: four
+// lane groups, M = 32: two) element j = 0..31 of the lane is
+//   6-bit and 4-bit formats:  k = 32*g + j              (K-contiguous)
+//   8-bit formats:            k = (K/2)*(j>>4) + 16*g + (j&15)
+// i.e. an 8-bit lane holds two runs of 16: words 0..3 from the first half of
+// K and words 4..7 from the second.  Element j sits at bits [w*j, w*j + w) of
+// the lane's little-endian operand string (w = 8: 8 words; w = 6: words 0..5,
+// 6 and 7 zero; w = 4: words 0..3, 4..7 zero).  One byte of a scale VGPR per
+// lane and operand, picked by op_sel: lane group g supplies the scale of K
+// block g (k in [32*g, 32*g + 32)) of its row / col for every format, so for
+// an 8-bit operand it is not the lane that holds those elements.  C/D use
+// the dtype-independent maps:
+//   16x16: row = (l>>4)*4 + r, col = l&15
+//   32x32: row = (r&3) + 8*(r>>2) + 4*(l>>5), col = l&31            r = 0..15
+//
+// Exactness.  Every operand is a small integer times a power of two and every
+// scale is a power of two, so each scaled product is an integer multiple of
+// q, the largest power of two that divides all of them.  With S the largest
+// sum of |a*b*sa*sb| over the outputs, any summation order is exact in f32
+// when S/q <= 2^24.  How wide the hardware aligns scaled products internally
+// is not documented, so the generator keeps S/q <= 2^kMxSpanBoundLog2 and
+// throws otherwise; the comparison is bitwise, with no tolerance.
+// ---------------------------------------------------------------------------
+
+constexpr int kMxFormats = 5;
+constexpr int kMxSets = 5;
+constexpr int kMxSpanBoundLog2 = 20;
+
+struct MxFormat {
+  const char* name;
+  int bits, ebits, mbits, bias;
+  int unit;      // alphabet values are mags[i] * 2^unit
+  int n_mags;
+  int mags[16];  // both signs of each are used
+  bool zero;     // plus zero
+};
+
+// Alphabets: both signs, every mantissa bit pattern, at least three exponent
+// values, magnitudes small enough for the span bound.  e2m1: all 15 values.
+static const MxFormat kMxFmt[kMxFormats] = {
+    {"e4m3", 8, 4, 3, 7, -3, 13, {1, 2, 3, 5, 8, 9, 10, 11, 12, 13, 14, 15, 16}, false},
+    {"e5m2", 8, 5, 2, 15, -2, 11, {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14}, false},
+    {"e2m3", 6, 2, 3, 1, -3, 16,
+     {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16}, false},
+    {"e3m2", 6, 3, 2, 3, -4, 12, {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16}, false},
+    {"e2m1", 4, 2, 1, 1, -1, 7, {1, 2, 3, 4, 6, 8, 12}, true},
+};
+
+// A code as (-1)^sign * mant * 2^exp; NaN / Inf codes are not finite.
+struct MxParts {
+  bool finite;
+  int sign, mant, exp;
+};
+
+static MxParts mx_decode_parts(int fmt, unsigned code) {
+  const MxFormat& f = kMxFmt[fmt];
+  const int e = (code >> f.mbits) & ((1 << f.ebits) - 1);
+  const int m = code & ((1 << f.mbits) - 1);
+  MxParts p{true, (int)((code >> (f.bits - 1)) & 1u), 0, 0};
+  if (fmt == 0 && e == 15 && m == 7) p.finite = false;  // e4m3 NaN
+  if (fmt == 1 && e == 31) p.finite = false;            // e5m2 Inf / NaN
+  if (e == 0) {
+    p.mant = m;  // subnormal
+    p.exp = 1 - f.bias - f.mbits;
+  } else {
+    p.mant = (1 << f.mbits) + m;
+    p.exp = e - f.bias - f.mbits;
+  }
+  return p;
+}
+
+static double mx_decode(int fmt, unsigned code) {
+  const MxParts p = mx_decode_parts(fmt, code);
+  const double v = std::ldexp((double)p.mant, p.exp);
+  return p.sign ? -v : v;
+}
+
+// Exact encoder of n * 2^unit: throws when no finite code has that value.
+static uint8_t mx_encode_exact(int fmt, int n, int unit) {
+  if (n == 0) return 0;
+  const int mag = n < 0 ? -n : n;
+  for (unsigned code = 0; code < (1u << kMxFmt[fmt].bits); ++code) {
+    const MxParts p = mx_decode_parts(fmt, code);
+    if (!p.finite || p.mant == 0 || p.sign != (n < 0)) continue;
+    const int d = p.exp - unit;
+    if (d >= 0 ? (d < 24 && (p.mant << d) == mag)
+               : (-d < 24 && (mag << -d) == p.mant))
+      return (uint8_t)code;
+  }
+  throw std::domain_error(std::string("mx_encode_exact: ") + kMxFmt[fmt].name +
+                          " cannot represent " + std::to_string(n) + " * 2^" +
+                          std::to_string(unit));
+}
+
+// E8M0: 2^(code - 127); 0xFF is NaN and never produced.
+static uint8_t mx_encode_e8m0(int exp) {
+  if (exp < -127 || exp > 127)
+    throw std::domain_error("mx_encode_e8m0: 2^" + std::to_string(exp) +
+                            " has no E8M0 code");
+  return (uint8_t)(exp + 127);
+}
+static double mx_decode_e8m0(uint8_t code) {
+  return std::ldexp(1.0, (int)code - 127);
+}
+
+// op_sel byte of the scale VGPR, per set: A and B use different bytes
+constexpr int mx_sel_a(int set) { return set & 3; }
+constexpr int mx_sel_b(int set) { return set == 0 ? 0 : 1 + (set % 3); }
+// scale exponents per set are base + one of three offsets: set 0 uniform, 1
+// and 2 near one, 3 far apart, 4 a wider spread that takes S/q near the bound
+static const int kMxScaleBaseA[kMxSets] = {0, -1, 2, 20, -2};
+static const int kMxScaleBaseB[kMxSets] = {0, 0, -3, -21, -1};
+static const int kMxScaleSpread[kMxSets][3] = {
+    {0, 0, 0}, {0, 1, 2}, {0, 1, 2}, {0, 1, 2}, {0, 1, 3}};
+
+struct MxProblem {
+  int set, fa, fb, shape;  // shape 0: 16x16x128, 1: 32x32x64
+  int m, n, k, kblocks, sel_a, sel_b;
+  std::vector<uint8_t> a_codes, b_codes;    // row-major m x k, k x n
+  std::vector<uint8_t> a_scales, b_scales;  // row-major m x kblocks, kblocks x n
+  std::vector<float> d;                     // expected, row-major m x n
+  double log2_span;                         // achieved log2(S / q)
+  std::vector<uint32_t> a_words, b_words;   // 64 lanes x 8 operand words
+  std::vector<uint32_t> a_scale_words, b_scale_words;  // 64 lanes
+};
+
+static const char* mx_shape_name(int shape) {
+  return shape == 0 ? "16x16x128" : "32x32x64";
+}
+
+// K index of element j of a lane in lane group g (see the layout above)
+static int mx_lane_k(int bits, int K, int g, int j) {
+  return bits == 8 ? (K / 2) * (j >> 4) + 16 * g + (j & 15) : 32 * g + j;
+}
+
+// One lane's 32 elements of row / col `codes` (K elements, `stride` apart):
+// element j at bits [w*j, w*j + w) of 8 words
+static void mx_pack_lane(int bits, int K, int g, const uint8_t* codes,
+                         size_t stride, uint32_t* words) {
+  for (int i = 0; i < 8; ++i) words[i] = 0;
+  for (int j = 0; j < 32; ++j) {
+    const uint32_t c = codes[mx_lane_k(bits, K, g, j) * stride];
+    const int pos = j * bits, w = pos >> 5, off = pos & 31;
+    words[w] |= c << off;
+    if (off + bits > 32) words[w + 1] |= c >> (32 - off);
+  }
+}
+
+static int mx_ctz(int64_t v) {
+  int z = 0;
+  while ((v & 1) == 0) {
+    v >>= 1;
+    ++z;
+  }
+  return z;
+}
+
+static MxProblem mx_problem(int set, int fa, int fb, int shape) {
+  if (set < 0 || set >= kMxSets)
+    throw std::invalid_argument("mx_problem: set out of range");
+  if (fa < 0 || fa >= kMxFormats || fb < 0 || fb >= kMxFormats)
+    throw std::invalid_argument("mx_problem: unknown format");
+  if (shape != 0 && shape != 1)
+    throw std::invalid_argument("mx_problem: unknown shape");
+  MxProblem p;
+  p.set = set;
+  p.fa = fa;
+  p.fb = fb;
+  p.shape = shape;
+  p.m = p.n = shape == 0 ? 16 : 32;
+  p.k = shape == 0 ? 128 : 64;
+  p.kblocks = p.k / 32;
+  p.sel_a = mx_sel_a(set);
+  p.sel_b = mx_sel_b(set);
+  const int M = p.m, N = p.n, K = p.k, KB = p.kblocks;
+
+  auto alphabet = [](int fmt) {
+    const MxFormat& f = kMxFmt[fmt];
+    std::vector<int> v;
+    for (int i = 0; i < f.n_mags; ++i) {
+      v.push_back(f.mags[i]);
+      v.push_back(-f.mags[i]);
+    }
+    if (f.zero) v.push_back(0);
+    return v;
+  };
+  const std::vector<int> al_a = alphabet(fa), al_b = alphabet(fb);
+  const int ua = kMxFmt[fa].unit, ub = kMxFmt[fb].unit;
+
+  // intended values (integers in units of 2^ua, 2^ub) and scale exponents;
+  // A and B are unrelated patterns and every (set, pair, shape) differs
+  std::vector<int> a(M * K), b(K * N), sa(M * KB), sb(KB * N);
+  for (int m = 0; m < M; ++m)
+    for (int k = 0; k < K; ++k)
+      a[m * K + k] = al_a[(m * 3 + k * 5 + set * 7 + fa * 2 + fb * 3 +
+                           shape * 11 + (m * k) % 5) % (int)al_a.size()];
+  for (int k = 0; k < K; ++k)
+    for (int n = 0; n < N; ++n)
+      b[k * N + n] = al_b[(k * 7 + n * 11 + set * 13 + fb * 4 + fa * 5 +
+                           shape * 3 + 3 + (k * n) % 7) % (int)al_b.size()];
+  // neighbouring rows / cols and neighbouring kblocks get different scales
+  // (set 0 is uniform: it checks the operand maps on their own)
+  for (int m = 0; m < M; ++m)
+    for (int kb = 0; kb < KB; ++kb)
+      sa[m * KB + kb] =
+          kMxScaleBaseA[set] + kMxScaleSpread[set][(m + 2 * kb + set) % 3];
+  for (int kb = 0; kb < KB; ++kb)
+    for (int n = 0; n < N; ++n)
+      sb[kb * N + n] =
+          kMxScaleBaseB[set] + kMxScaleSpread[set][(2 * n + kb + set + 1) % 3];
+
+  // encode; an operand that does not round-trip throws
+  p.a_codes.resize(M * K);
+  p.b_codes.resize(K * N);
+  p.a_scales.resize(M * KB);
+  p.b_scales.resize(KB * N);
+  for (int i = 0; i < M * K; ++i) {
+    p.a_codes[i] = mx_encode_exact(fa, a[i], ua);
+    if (mx_decode(fa, p.a_codes[i]) != std::ldexp((double)a[i], ua))
+      throw std::domain_error("mx_problem: A operand does not round-trip");
+  }
+  for (int i = 0; i < K * N; ++i) {
+    p.b_codes[i] = mx_encode_exact(fb, b[i], ub);
+    if (mx_decode(fb, p.b_codes[i]) != std::ldexp((double)b[i], ub))
+      throw std::domain_error("mx_problem: B operand does not round-trip");
+  }
+  for (int i = 0; i < M * KB; ++i) {
+    p.a_scales[i] = mx_encode_e8m0(sa[i]);
+    if (mx_decode_e8m0(p.a_scales[i]) != std::ldexp(1.0, sa[i]))
+      throw std::domain_error("mx_problem: A scale does not round-trip");
+  }
+  for (int i = 0; i < KB * N; ++i) {
+    p.b_scales[i] = mx_encode_e8m0(sb[i]);
+    if (mx_decode_e8m0(p.b_scales[i]) != std::ldexp(1.0, sb[i]))
+      throw std::domain_error("mx_problem: B scale does not round-trip");
+  }
+
+  // expected tile in 64-bit fixed point with unit 2^e_min, from the intended
+  // integers and exponents (never from decoded floats)
+  int e_min = INT32_MAX;
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < N; ++n)
+      for (int kb = 0; kb < KB; ++kb)
+        e_min = std::min(e_min, ua + ub + sa[m * KB + kb] + sb[kb * N + n]);
+  int q_exp = INT32_MAX;  // log2 of q
+  int64_t s_max = 0;      // S in units of 2^e_min
+  p.d.resize(M * N);
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < N; ++n) {
+      int64_t acc = 0, abs_sum = 0;
+      for (int k = 0; k < K; ++k) {
+        const int64_t prod = (int64_t)a[m * K + k] * b[k * N + n];
+        if (prod == 0) continue;
+        const int e = ua + ub + sa[m * KB + k / 32] + sb[(k / 32) * N + n];
+        if (e - e_min > 30) throw std::domain_error("mx_problem: scale spread");
+        acc += prod * ((int64_t)1 << (e - e_min));
+        abs_sum += (prod < 0 ? -prod : prod) * ((int64_t)1 << (e - e_min));
+        q_exp = std::min(q_exp, e + mx_ctz(prod));
+      }
+      s_max = std::max(s_max, abs_sum);
+      const double want = std::ldexp((double)acc, e_min);
+      p.d[m * N + n] = (float)want;
+      if ((double)p.d[m * N + n] != want)
+        throw std::domain_error("mx_problem: expected value is not an f32");
+    }
+  if (s_max == 0) throw std::domain_error("mx_problem: empty tile");
+  p.log2_span = std::log2((double)s_max) + (double)(e_min - q_exp);
+  if (p.log2_span > (double)kMxSpanBoundLog2)
+    throw std::domain_error(
+        std::string("mx_problem: S/q = 2^") + std::to_string(p.log2_span) +
+        " exceeds the exactness bound for " + kMxFmt[fa].name + " x " +
+        kMxFmt[fb].name + " " + mx_shape_name(shape) + " set " +
+        std::to_string(set));
+
+  // per-lane fragments; the three scale bytes op_sel does not pick hold valid
+  // scales that would give another answer
+  p.a_words.resize(64 * 8);
+  p.b_words.resize(64 * 8);
+  p.a_scale_words.resize(64);
+  p.b_scale_words.resize(64);
+  for (int l = 0; l < 64; ++l) {
+    const int rc = l % M, kb = l / M;
+    mx_pack_lane(kMxFmt[fa].bits, K, kb, &p.a_codes[rc * K], 1,
+                 &p.a_words[l * 8]);
+    mx_pack_lane(kMxFmt[fb].bits, K, kb, &p.b_codes[rc], (size_t)N,
+                 &p.b_words[l * 8]);
+    const uint32_t ca = p.a_scales[rc * KB + kb], cb = p.b_scales[kb * N + rc];
+    uint32_t wa = 0, wb = 0;
+    for (int i = 0; i < 4; ++i) {
+      wa |= (i == p.sel_a ? ca : ca + 3 + i) << (8 * i);
+      wb |= (i == p.sel_b ? cb : cb + 3 + i) << (8 * i);
+    }
+    p.a_scale_words[l] = wa;
+    p.b_scale_words[l] = wb;
+  }
+  return p;
+}
+
+// The sweep's problems per set: five same-format pairs and three mixed pairs
+// (cbsz != blgp) on 16x16x128, then e2m1 and e4m3 on 32x32x64.
+constexpr int kMxProbs = 10;
+constexpr int kMxProbFa[kMxProbs] = {0, 1, 2, 3, 4, 0, 4, 3, 4, 0};
+constexpr int kMxProbFb[kMxProbs] = {0, 1, 2, 3, 4, 4, 2, 1, 4, 0};
+constexpr int kMxProbShape[kMxProbs] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1};
+constexpr int kMxProbBit[kMxProbs] = {0, 1, 2, 3, 4, 5, 5, 5, 6, 6};
+constexpr int kMxFailBits = 7;  // e4m3 e5m2 e2m3 e3m2 e2m1 mixed shape32
+
+using i32x8 = __attribute__((ext_vector_type(8))) int;
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+#if defined(__gfx950__)
+template <int FA, int FB, int OA, int OB>
+__device__ __forceinline__ f32x4 mx16(i32x8 a, i32x8 b, f32x4 c, int sa, int sb) {
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FA, FB, OA,
+                                                          sa, OB, sb);
+}
+template <int FA, int FB, int OA, int OB>
+__device__ __forceinline__ f32x16 mx32(i32x8 a, i32x8 b, f32x16 c, int sa, int sb) {
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, FA, FB, OA,
+                                                         sa, OB, sb);
+}
+#endif
+
+// Single tile: one wave, one instruction.  rec = 64 lanes x {a[8], b[8], sa,
+// sb}; out = 64 lanes x 16 accumulator registers (4 used by 16x16).  The
+// format pair is a run-time argument, so every cbsz / blgp pair has a case.
+constexpr int kMxTileRecWords = 18;
+
+#define MX_TILE_CASE(FN, FA, FB)                                            \
+  case FA * kMxFormats + FB:                                                \
+    d = FN<FA, FB, mx_sel_a(SET), mx_sel_b(SET)>(a, b, d, sa, sb);          \
+    break;
+#define MX_TILE_ROW(FN, FA)                                                 \
+  MX_TILE_CASE(FN, FA, 0) MX_TILE_CASE(FN, FA, 1) MX_TILE_CASE(FN, FA, 2)   \
+  MX_TILE_CASE(FN, FA, 3) MX_TILE_CASE(FN, FA, 4)
+#define MX_TILE_CASES(FN)                                                   \
+  MX_TILE_ROW(FN, 0) MX_TILE_ROW(FN, 1) MX_TILE_ROW(FN, 2)                  \
+  MX_TILE_ROW(FN, 3) MX_TILE_ROW(FN, 4)
+
+template <int SHAPE, int SET>
+__global__ void mx_tile_kernel(const uint32_t* __restrict__ rec,
+                               float* __restrict__ out, int pair) {
+#if defined(__gfx950__)
+  const int lane = threadIdx.x;  // one wave of 64
+  const uint32_t* p = rec + lane * kMxTileRecWords;
+  i32x8 a, b;
+  for (int i = 0; i < 8; ++i) {
+    a[i] = (int)p[i];
+    b[i] = (int)p[8 + i];
+  }
+  const int sa = (int)p[16], sb = (int)p[17];
+  if constexpr (SHAPE == 0) {
+    f32x4 d = {0.f, 0.f, 0.f, 0.f};
+    switch (pair) { MX_TILE_CASES(mx16) }
+    for (int r = 0; r < 4; ++r) out[lane * 16 + r] = d[r];
+  } else {
+    f32x16 d = {0.f};
+    switch (pair) { MX_TILE_CASES(mx32) }
+    for (int r = 0; r < 16; ++r) out[lane * 16 + r] = d[r];
+  }
+#endif
+}
+
+static int mx_format_index(const std::string& name) {
+  for (int f = 0; f < kMxFormats; ++f)
+    if (name == kMxFmt[f].name) return f;
+  throw std::invalid_argument("unknown MX format '" + name +
+                              "' (e4m3, e5m2, e2m3, e3m2, e2m1)");
+}
+static int mx_shape_index(const std::string& name) {
+  for (int s = 0; s < 2; ++s)
+    if (name == mx_shape_name(s)) return s;
+  throw std::invalid_argument("unknown MX shape '" + name +
+                              "' (16x16x128, 32x32x64)");
+}
+
+static py::dict mx_problem_dict(const MxProblem& p) {
+  py::dict e;
+  e["set"] = p.set;
+  e["fmt_a"] = std::string(kMxFmt[p.fa].name);
+  e["fmt_b"] = std::string(kMxFmt[p.fb].name);
+  e["shape"] = std::string(mx_shape_name(p.shape));
+  e["m"] = p.m;
+  e["n"] = p.n;
+  e["k"] = p.k;
+  e["op_sel_a"] = p.sel_a;
+  e["op_sel_b"] = p.sel_b;
+  e["a_codes"] = std::vector<int>(p.a_codes.begin(), p.a_codes.end());
+  e["b_codes"] = std::vector<int>(p.b_codes.begin(), p.b_codes.end());
+  e["a_scales"] = std::vector<int>(p.a_scales.begin(), p.a_scales.end());
+  e["b_scales"] = std::vector<int>(p.b_scales.begin(), p.b_scales.end());
+  e["d"] = p.d;
+  e["log2_span"] = p.log2_span;
+  e["a_words"] = p.a_words;  // 64 lanes x 8, as packed for the instruction
+  e["b_words"] = p.b_words;
+  e["a_scale_words"] = p.a_scale_words;
+  e["b_scale_words"] = p.b_scale_words;
+  return e;
+}
+
+static py::dict mx_reference() {
+  // host only: no HIP call
+  py::dict out;
+  out["sets"] = kMxSets;
+  out["span_bound_log2"] = kMxSpanBoundLog2;
+  py::list problems;
+  for (int s = 0; s < kMxSets; ++s)
+    for (int i = 0; i < kMxProbs; ++i)
+      problems.append(mx_problem_dict(
+          mx_problem(s, kMxProbFa[i], kMxProbFb[i], kMxProbShape[i])));
+  out["problems"] = problems;
+  return out;
+}
+
+template <int SHAPE>
+static void mx_tile_launch(int set, const uint32_t* rec, float* out, int pair) {
+  switch (set) {
+    case 0:
+      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 0>), dim3(1), dim3(64), 0, 0, rec, out, pair);
+      break;
+    case 1:
+      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 1>), dim3(1), dim3(64), 0, 0, rec, out, pair);
+      break;
+    case 2:
+      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 2>), dim3(1), dim3(64), 0, 0, rec, out, pair);
+      break;
+    case 3:
+      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 3>), dim3(1), dim3(64), 0, 0, rec, out, pair);
+      break;
+    default:
+      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 4>), dim3(1), dim3(64), 0, 0, rec, out, pair);
+      break;
+  }
+}
+
+static py::dict mx_mfma_tile(int device, const std::string& fmt_a,
+                             const std::string& fmt_b, const std::string& shape,
+                             int set) {
+  // Run one scaled MFMA and return the raw problem + the GPU tile so Python
+  // tests can verify against independent decoders.
+  const int fa = mx_format_index(fmt_a), fb = mx_format_index(fmt_b);
+  const int sh = mx_shape_index(shape);
+  const MxProblem p = mx_problem(set, fa, fb, sh);  // validates set
+  std::vector<uint32_t> rec((size_t)64 * kMxTileRecWords);
+  for (int l = 0; l < 64; ++l) {
+    uint32_t* r = &rec[(size_t)l * kMxTileRecWords];
+    std::memcpy(r, &p.a_words[l * 8], 32);
+    std::memcpy(r + 8, &p.b_words[l * 8], 32);
+    r[16] = p.a_scale_words[l];
+    r[17] = p.b_scale_words[l];
+  }
+  HIP_CHECK(hipSetDevice(device));
+  CovDeviceBuf d_rec, d_out;
+  d_rec.alloc(sizeof(uint32_t) * rec.size());
+  d_out.alloc(sizeof(float) * 64 * 16);
+  HIP_CHECK(hipMemcpy(d_rec.ptr, rec.data(), sizeof(uint32_t) * rec.size(),
+                      hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_out.ptr, 0xFF, sizeof(float) * 64 * 16));
+  if (sh == 0)
+    mx_tile_launch<0>(set, d_rec.u32(), static_cast<float*>(d_out.ptr),
+                      fa * kMxFormats + fb);
+  else
+    mx_tile_launch<1>(set, d_rec.u32(), static_cast<float*>(d_out.ptr),
+                      fa * kMxFormats + fb);
+  HIP_CHECK(hipGetLastError());
+  std::vector<float> regs(64 * 16);
+  HIP_CHECK(hipMemcpy(regs.data(), d_out.ptr, sizeof(float) * regs.size(),
+                      hipMemcpyDeviceToHost));
+  std::vector<float> d_gpu((size_t)p.m * p.n);
+  for (int l = 0; l < 64; ++l)
+    for (int r = 0; r < (sh == 0 ? 4 : 16); ++r) {
+      const int row = sh == 0 ? (l >> 4) * 4 + r
+                              : (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+      const int col = sh == 0 ? (l & 15) : (l & 31);
+      d_gpu[row * p.n + col] = regs[l * 16 + r];
+    }
+  py::dict out = mx_problem_dict(p);
+  out["d_gpu"] = d_gpu;  // GPU result, row-major m x n
+  return out;
+}
+
+// Whole-device MX sweep, built like cu_coverage_kernel: same grid, launch
+// bounds, 64 KiB LDS claim, placement key and slot scheme, fixed work per
+// workgroup.  Per-lane record of one (set, problem): a[8] b[8] sa sb exp[16]
+// (16x16 problems use exp[0..3]).
+constexpr int kMxRecWords = 34;
+
+template <int SET, int P>
+__device__ __forceinline__ unsigned mx_cov_problem(const uint32_t* tab, int lane,
+                                                   unsigned pm) {
+  unsigned fail = 0;
+#if defined(__gfx950__)
+  constexpr int FA = kMxProbFa[P], FB = kMxProbFb[P], BIT = kMxProbBit[P];
+  // volatile: operands and expected values are re-read from global memory
+  // every repetition, so neither the MFMA nor the compare can be hoisted
+  const uint32_t* rec =
+      tab + (size_t)((SET * kMxProbs + P) * 64 + lane) * kMxRecWords;
+  // opaque to the optimizer: otherwise the address of every word of every
+  // record is loop-invariant, gets hoisted out of the repetition loop and
+  // spills; this way each record is one base plus immediate offsets
+  asm volatile("" : "+v"(rec));
+  const volatile uint32_t* p = rec;
+  i32x8 a, b;
+  for (int i = 0; i < 8; ++i) {
+    a[i] = (int)p[i];
+    b[i] = (int)p[8 + i];
+  }
+  const int sa = (int)p[16], sb = (int)p[17];
+  const uint32_t px = (pm >> BIT) & 1u;  // test hook: flips an expected bit
+  if constexpr (kMxProbShape[P] == 0) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 d = mx16<FA, FB, mx_sel_a(SET), mx_sel_b(SET)>(a, b, zero, sa, sb);
+    for (int r = 0; r < 4; ++r)
+      if (__float_as_uint(d[r]) != (p[18 + r] ^ px)) fail = 1u << BIT;
+  } else {
+    const f32x16 zero = {0.f};
+    const f32x16 d = mx32<FA, FB, mx_sel_a(SET), mx_sel_b(SET)>(a, b, zero, sa, sb);
+    for (int r = 0; r < 16; ++r)
+      if (__float_as_uint(d[r]) != (p[18 + r] ^ px)) fail = 1u << BIT;
+  }
+#endif
+  return fail;
+}
+
+template <int SET>
+__device__ __forceinline__ unsigned mx_cov_set(const uint32_t* tab, int lane,
+                                               unsigned pm) {
+  return mx_cov_problem<SET, 0>(tab, lane, pm) | mx_cov_problem<SET, 1>(tab, lane, pm) |
+         mx_cov_problem<SET, 2>(tab, lane, pm) | mx_cov_problem<SET, 3>(tab, lane, pm) |
+         mx_cov_problem<SET, 4>(tab, lane, pm) | mx_cov_problem<SET, 5>(tab, lane, pm) |
+         mx_cov_problem<SET, 6>(tab, lane, pm) | mx_cov_problem<SET, 7>(tab, lane, pm) |
+         mx_cov_problem<SET, 8>(tab, lane, pm) | mx_cov_problem<SET, 9>(tab, lane, pm);
+}
+static_assert(kMxProbs == 10 && kMxSets == 5, "mx_cov_set / mx_coverage_kernel");
+
+__global__ void __launch_bounds__(kCovBlock, kCovBlocksPerCu)
+mx_coverage_kernel(const uint32_t* tab, uint32_t* __restrict__ slot_waves,
+                   uint32_t* __restrict__ slot_fail,
+                   uint32_t* __restrict__ slot_hw_id,
+                   uint32_t* __restrict__ slot_xcc_id, int reps, int poison_key,
+                   unsigned poison_mask, int poison_all) {
+#if defined(__gfx950__)
+  __shared__ uint32_t lds[kCovLdsWords];  // the claim that keeps 2 per CU
+  const uint32_t hw_id = __builtin_amdgcn_s_getreg(kCovHwRegHwId);
+  const uint32_t xcc_id = __builtin_amdgcn_s_getreg(kCovHwRegXccId);
+  const uint32_t key = ((xcc_id & 0xFu) << 8) | ((hw_id >> 8) & 0xFFu);
+  const uint32_t simd = (hw_id >> 4) & 3u;
+  const unsigned pm = (poison_all || (int)key == poison_key) ? poison_mask : 0u;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  unsigned fail = 0;
+#pragma unroll 1
+  for (int rep = 0; rep < reps; ++rep) {
+    fail |= mx_cov_set<0>(tab, lane, pm);
+    fail |= mx_cov_set<1>(tab, lane, pm);
+    fail |= mx_cov_set<2>(tab, lane, pm);
+    fail |= mx_cov_set<3>(tab, lane, pm);
+    fail |= mx_cov_set<4>(tab, lane, pm);
+  }
+
+  // the masks pass through LDS once (neighbouring lanes swap theirs), which
+  // keeps the static claim alive; the wave-wide OR below makes it a no-op
+  lds[tid * 64] = fail;  // tid < 256: index < kCovLdsWords
+  __syncthreads();
+  fail |= lds[(tid ^ 1) * 64];
+
+  unsigned wave_fail = 0;
+  for (int b = 0; b < kMxFailBits; ++b)
+    if (__ballot((fail >> b) & 1u) != 0) wave_fail |= 1u << b;
+  if (lane == 0) {
+    const uint32_t slot = key * 4u + simd;  // < kCovSlots by the masks above
+    atomicAdd(&slot_waves[slot], 1u);
+    if (wave_fail) atomicOr(&slot_fail[slot], wave_fail);
+    slot_hw_id[slot] = hw_id;
+    slot_xcc_id[slot] = xcc_id;
+  }
+#endif
+}
+
+static std::vector<uint32_t> mx_build_table() {
+  std::vector<uint32_t> tab((size_t)kMxSets * kMxProbs * 64 * kMxRecWords, 0u);
+  for (int s = 0; s < kMxSets; ++s)
+    for (int i = 0; i < kMxProbs; ++i) {
+      const MxProblem p =
+          mx_problem(s, kMxProbFa[i], kMxProbFb[i], kMxProbShape[i]);
+      for (int l = 0; l < 64; ++l) {
+        uint32_t* r = &tab[(size_t)((s * kMxProbs + i) * 64 + l) * kMxRecWords];
+        std::memcpy(r, &p.a_words[l * 8], 32);
+        std::memcpy(r + 8, &p.b_words[l * 8], 32);
+        r[16] = p.a_scale_words[l];
+        r[17] = p.b_scale_words[l];
+        for (int q = 0; q < (p.shape == 0 ? 4 : 16); ++q) {
+          const int row = p.shape == 0 ? (l >> 4) * 4 + q
+                                       : (q & 3) + 8 * (q >> 2) + 4 * (l >> 5);
+          const int col = p.shape == 0 ? (l & 15) : (l & 31);
+          r[18 + q] = cov_f32_bits(p.d[row * p.n + col]);
+        }
+      }
+    }
+  return tab;
+}
+
+static py::dict mx_coverage_check(int device, int reps, int max_rounds,
+                                  int poison_key, unsigned poison_mask,
+                                  bool poison_all) {
+  return cov_run_sweep(
+      "mx_coverage_check", device, reps, max_rounds, poison_key, poison_mask,
+      kMxFailBits, mx_build_table(),
+      [&](int cus, uint32_t* tab, uint32_t* slots) {
+        hipLaunchKernelGGL(mx_coverage_kernel, dim3(kCovBlocksPerCu * cus),
+                           dim3(kCovBlock), 0, 0, tab, slots, slots + kCovSlots,
+                           slots + 2 * kCovSlots, slots + 3 * kCovSlots, reps,
+                           poison_key, poison_mask, poison_all ? 1 : 0);
+      });
+}
+
+// MX burn-in: the analogue of mfma_burn_kernel on 16x16x128, e2m1 or e4m3,
+// four independent accumulators per wave.  Operands are non-zero alphabet
+// codes; both scales are 2^-20, so the accumulators stay finite.
+template <int FMT>
+__global__ void mx_burn_kernel(const uint32_t* __restrict__ seed,
+                               float* __restrict__ out, int iters) {
+#if defined(__gfx950__)
+  const int lane = threadIdx.x & 63;
+  i32x8 a, b;
+  for (int i = 0; i < 8; ++i) {
+    a[i] = (int)seed[lane * 16 + i];
+    b[i] = (int)seed[lane * 16 + 8 + i];
+  }
+  const int sc = (int)seed[64 * 16];
+  f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+  f32x4 acc2 = {0, 0, 0, 0}, acc3 = {0, 0, 0, 0};
+  for (int i = 0; i < iters; ++i) {
+    acc0 = mx16<FMT, FMT, 0, 0>(a, b, acc0, sc, sc);
+    acc1 = mx16<FMT, FMT, 0, 0>(a, b, acc1, sc, sc);
+    acc2 = mx16<FMT, FMT, 0, 0>(a, b, acc2, sc, sc);
+    acc3 = mx16<FMT, FMT, 0, 0>(a, b, acc3, sc, sc);
+  }
+  const float sink = acc0[0] + acc1[1] + acc2[2] + acc3[3];
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  out[tid] = sink;  // keep the loop alive
+#endif
+}
+
+static double mx_throughput_tflops(int device, const std::string& fmt, int iters) {
+  const int f = mx_format_index(fmt);
+  if (f != 0 && f != 4)
+    throw std::invalid_argument("mx_throughput_tflops: fmt must be e2m1 or e4m3");
+  if (iters < 1 || iters > 10000000)
+    throw std::invalid_argument("mx_throughput_tflops: iters must be in [1, 1e7]");
+  // 64 lanes x {a[8], b[8]} of non-zero alphabet codes, then the scale word
+  const MxFormat& mf = kMxFmt[f];
+  std::vector<uint32_t> hseed(64 * 16 + 1);
+  for (int l = 0; l < 64; ++l)
+    for (int h = 0; h < 2; ++h) {
+      uint8_t codes[128];  // one row: only the lane's own 32 are read
+      for (int j = 0; j < 128; ++j) {
+        const int mag = mf.mags[(l * 7 + j * 3 + h * 5) % mf.n_mags];
+        codes[j] = mx_encode_exact(f, (l + j + h) % 3 == 0 ? -mag : mag, mf.unit);
+      }
+      mx_pack_lane(mf.bits, 128, l >> 4, codes, 1, &hseed[l * 16 + h * 8]);
+    }
+  hseed[64 * 16] = 0x01010101u * mx_encode_e8m0(-20);
+  const int block = 256, grid = 512;  // 2048 waves = 2 per SIMD, 4 chains each
+  HIP_CHECK(hipSetDevice(device));
+  CovDeviceBuf d_seed, d_out;
+  d_seed.alloc(sizeof(uint32_t) * hseed.size());
+  d_out.alloc(sizeof(float) * block * grid);
+  HIP_CHECK(hipMemcpy(d_seed.ptr, hseed.data(), sizeof(uint32_t) * hseed.size(),
+                      hipMemcpyHostToDevice));
+  auto launch = [&](int n) {
+    if (f == 4)
+      hipLaunchKernelGGL(mx_burn_kernel<4>, dim3(grid), dim3(block), 0, 0,
+                         d_seed.u32(), static_cast<float*>(d_out.ptr), n);
+    else
+      hipLaunchKernelGGL(mx_burn_kernel<0>, dim3(grid), dim3(block), 0, 0,
+                         d_seed.u32(), static_cast<float*>(d_out.ptr), n);
+  };
+  launch(1000);  // warmup
+  HIP_CHECK(hipDeviceSynchronize());
+  CovEvent t0, t1;
+  t0.create();
+  t1.create();
+  HIP_CHECK(hipEventRecord(t0.ev));
+  launch(iters);
+  HIP_CHECK(hipEventRecord(t1.ev));
+  HIP_CHECK(hipEventSynchronize(t1.ev));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+  const double waves = (double)grid * block / 64.0;
+  const double flop = waves * (double)iters * 4.0 * (16.0 * 16.0 * 128.0 * 2.0);
+  return flop / 1e12 / ((double)ms / 1e3);
 }
 
 // ---------------------------------------------------------------------------
@@ -1418,6 +2148,25 @@ PYBIND11_MODULE(_gpu_validator, m) {
         py::arg("poison_all") = false,
         "Whole-device sweep: f32/bf16/fp8 MFMA tiles + LDS round trip on every "
         "CU and SIMD, exact comparison, results per placement key");
+  m.def("mx_coverage_check", &mx_coverage_check, py::arg("device") = 0,
+        py::arg("reps") = 16, py::arg("max_rounds") = 8,
+        py::arg("poison_key") = -1, py::arg("poison_mask") = 0u,
+        py::arg("poison_all") = false,
+        "Whole-device sweep of the MX block-scaled MFMA path (five formats, "
+        "mixed pairs, both shapes) on every CU and SIMD, exact comparison, "
+        "results per placement key");
+  m.def("mx_reference", &mx_reference,
+        "Host-only: the MX sweep's problems as raw operand and scale codes, "
+        "packed lane words, expected tiles and achieved log2(S/q)");
+  m.def("mx_mfma_tile", &mx_mfma_tile, py::arg("device") = 0,
+        py::arg("fmt_a") = "e2m1", py::arg("fmt_b") = "e2m1",
+        py::arg("shape") = "16x16x128", py::arg("set") = 0,
+        "Run one scaled MFMA tile; returns the raw problem + GPU output for "
+        "independent verification");
+  m.def("mx_throughput_tflops", &mx_throughput_tflops, py::arg("device") = 0,
+        py::arg("fmt") = "e2m1", py::arg("iters") = 20000,
+        "Sustained MX (e2m1 or e4m3, 16x16x128) matrix-core throughput in "
+        "TFLOP/s (burn-in check)");
   m.def("cu_coverage_reference", &cu_coverage_reference,
         "Host-only: the sweep's operand sets (decoded to f32) and expected "
         "tiles per dtype");

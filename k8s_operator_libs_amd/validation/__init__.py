@@ -18,7 +18,12 @@ Layers:
   unit that produced them (:func:`summarize_cu_coverage` is the pure verdict);
 - :func:`hbm_integrity_check` — opt-in moving-inversions pattern test over a
   region of HBM: exact comparison, coverage counted, failing words recorded
-  (:func:`summarize_hbm_integrity` is the pure verdict).
+  (:func:`summarize_hbm_integrity` is the pure verdict);
+- :func:`mx_matrix_check` — opt-in whole-device sweep of the MX block-scaled
+  matrix path (``v_mfma_scale_f32_*_f8f6f4``: e4m3, e5m2, e2m3, e3m2 and e2m1
+  operands with E8M0 block scales, both shapes, mixed pairs), bit-exact, with
+  failures attributed per unit (:func:`summarize_mx_matrix` is the pure
+  verdict).
 """
 
 from .gpu_health import (  # noqa: F401
@@ -34,4 +39,8 @@ from .cu_coverage import (  # noqa: F401
 from .hbm_integrity import (  # noqa: F401
     hbm_integrity_check,
     summarize_hbm_integrity,
+)
+from .mx_matrix import (  # noqa: F401
+    mx_matrix_check,
+    summarize_mx_matrix,
 )

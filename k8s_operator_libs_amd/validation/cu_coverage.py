@@ -19,7 +19,7 @@ as a count mismatch (unhealthy), never as coverage that was not achieved.
 
 from __future__ import annotations
 
-from typing import Any, Dict, List
+from typing import Any, Dict, List, Sequence
 
 from .gpu_health import GpuHealthError, load_native_validator
 
@@ -42,8 +42,8 @@ def decode_key(key: int) -> Dict[str, int]:
     }
 
 
-def _failed_names(mask: int) -> List[str]:
-    return [name for bit, name in enumerate(FAIL_BITS) if mask & (1 << bit)]
+def _failed_names(mask: int, fail_bits: Sequence[str]) -> List[str]:
+    return [name for bit, name in enumerate(fail_bits) if mask & (1 << bit)]
 
 
 def summarize_cu_coverage(raw: Dict[str, Any]) -> Dict[str, Any]:
@@ -54,6 +54,12 @@ def summarize_cu_coverage(raw: Dict[str, Any]) -> Dict[str, Any]:
     slot has a non-zero ``fail_mask``, every compute unit was seen and every
     one of them was seen on all four SIMDs.
     """
+    return summarize_sweep(raw, FAIL_BITS)
+
+
+def summarize_sweep(raw: Dict[str, Any], fail_bits: Sequence[str]) -> Dict[str, Any]:
+    """The verdict of a whole-device sweep whose ``fail_mask`` bits are named,
+    in bit order, by ``fail_bits`` (shared with :mod:`.mx_matrix`)."""
     compute_units = int(raw["compute_units"])
     units = [dict(u) for u in raw.get("units", [])]
 
@@ -75,7 +81,7 @@ def summarize_cu_coverage(raw: Dict[str, Any]) -> Dict[str, Any]:
             continue
         entry = decode_key(int(u["key"]))
         entry.update(
-            key=int(u["key"]), simd=int(u["simd"]), failed=_failed_names(mask)
+            key=int(u["key"]), simd=int(u["simd"]), failed=_failed_names(mask, fail_bits)
         )
         failing_units.append(entry)
 

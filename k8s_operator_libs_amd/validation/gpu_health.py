@@ -90,13 +90,17 @@ def gpu_health_check(
     coverage: bool = False,
     memory: bool = False,
     memory_mib: float = 4096.0,
+    mx: bool = False,
 ) -> Dict[str, Any]:
     """Full node GPU health check.  Returns a report dict with a top-level
     ``healthy`` verdict; raises GpuHealthError when ``require_gpu`` and no
     usable GPU/native validator is present.  ``coverage`` adds the
     whole-device per-CU sweep (see :mod:`.cu_coverage`) and gates the verdict
     on it.  ``memory`` adds the HBM pattern test over ``memory_mib`` MiB
-    (``0``: all free memory; see :mod:`.hbm_integrity`) and gates on it too."""
+    (``0``: all free memory; see :mod:`.hbm_integrity`) and gates on it too.
+    ``mx`` adds the whole-device sweep of the MX block-scaled matrix path and
+    its e2m1 / e4m3 burn-in (see :mod:`.mx_matrix`); the verdict is gated on
+    the sweep and on each throughput reaching ``MFMA_MIN_TFLOPS``."""
     report: Dict[str, Any] = {"healthy": False, "checks": {}}
     report["checks"]["smi"] = smi_probe()
 
@@ -152,6 +156,28 @@ def gpu_health_check(
         report["checks"]["hbm_integrity"] = mem
         memory_ok = mem["healthy"]
 
+    mx_ok = True
+    if mx:
+        # opt-in: MX block-scaled MFMA on every CU and SIMD + MX burn-in.  The
+        # floor is the bf16 one: an MX path slower than bf16 is broken
+        # whatever its true peak is
+        from .mx_matrix import (
+            THROUGHPUT_FORMATS,
+            THROUGHPUT_ITERS,
+            summarize_mx_matrix,
+        )
+
+        mx_summary = summarize_mx_matrix(native.mx_coverage_check(device))
+        mx_summary["throughput_tflops"] = {
+            fmt: native.mx_throughput_tflops(device, fmt, THROUGHPUT_ITERS)
+            for fmt in THROUGHPUT_FORMATS
+        }
+        report["checks"]["mx_matrix"] = mx_summary
+        mx_ok = mx_summary["healthy"] and all(
+            tf >= MFMA_MIN_TFLOPS
+            for tf in mx_summary["throughput_tflops"].values()
+        )
+
     # multi-GPU nodes: verify every xGMI peer link is up
     xgmi_ok = True
     if probe.get("device_count", 1) > 1:
@@ -170,6 +196,7 @@ def gpu_health_check(
         and deep_ok
         and coverage_ok
         and memory_ok
+        and mx_ok
     )
     return report
 
@@ -178,7 +205,8 @@ def main() -> int:
     """CLI entry point for use inside a validation pod.  Pass ``--deep`` for
     the fp8 + burn-in checks, ``--coverage`` for the per-CU sweep and
     ``--memory`` for the HBM pattern test (``--memory-mib=N`` sets its size
-    and implies it; ``N=0`` means all free memory)."""
+    and implies it; ``N=0`` means all free memory) and ``--mx`` for the MX
+    block-scaled matrix sweep and burn-in."""
     import sys
 
     memory_kw: Dict[str, Any] = {}
@@ -192,6 +220,7 @@ def main() -> int:
         require_gpu=True,
         deep="--deep" in sys.argv,
         coverage="--coverage" in sys.argv,
+        mx="--mx" in sys.argv,
         **memory_kw,
     )
     print(json.dumps(report, indent=2, default=str))  # noqa: T201 (CLI/build output)
