@@ -22,6 +22,17 @@ from .errors import ApiError
 from .fakecluster import FakeCluster
 
 
+#: threaded engine, with the ``_wire`` extension: the thread that mutates the
+#: cluster writes each watch event to the watchers' sockets itself
+#: (``_wire.StreamWriter``) and the per-stream thread only keeps time.  False
+#: restores the queue hand-off to the per-stream thread.
+WATCH_FANOUT = True
+
+#: bytes a watch stream may hold for a reader that has fallen behind before
+#: the server cuts it off (None: the extension's default, 64 MiB)
+WATCH_MAX_BACKLOG = None
+
+
 def _status_body(exc: ApiError) -> dict:
     reason = {
         404: "NotFound",
@@ -650,6 +661,66 @@ def _make_threaded_server(host, port, cluster):
             self.close_connection = True
             deadline = time.monotonic() + timeout_s if timeout_s else None
             last_bookmark = None
+
+            def bookmark_line(rv) -> bytes:
+                return (json.dumps({
+                    "type": "BOOKMARK",
+                    "object": {"kind": kind,
+                               "apiVersion": api_version,
+                               "metadata": {"resourceVersion": rv}},
+                }) + "\n").encode()
+
+            writer_cls = getattr(wire, "StreamWriter", None)
+            if writer_cls is not None and WATCH_FANOUT:
+                # direct fan-out: the thread that mutates the cluster writes
+                # the event line to this socket itself (non-blocking, backlog
+                # drained natively), so an event costs no thread hand-off.
+                # This thread is left with deadlines, shutdown, bookmarks and
+                # keep-alives, all through the same writer.
+                self.wfile.flush()
+                fd = self.connection.fileno()
+                writer = (writer_cls(fd) if WATCH_MAX_BACKLOG is None
+                          else writer_cls(fd, WATCH_MAX_BACKLOG))
+
+                def sink(event_type, snapshot):
+                    writer.write(cluster.event_line(event_type, snapshot))
+
+                try:
+                    with cluster._lock:
+                        # what cluster.watch() queued (resume replay, initial
+                        # events and their bookmark) and anything since, then
+                        # the sink: no event can fall in between
+                        while True:
+                            item = watch.next(timeout=0)
+                            if item is None:
+                                break
+                            writer.write((json.dumps(
+                                {"type": item[0], "object": item[1]})
+                                + "\n").encode())
+                        watch.set_sink(sink)
+                    while not (getattr(server, "_shutting_down", False)
+                               or writer.dead):
+                        if deadline is not None and time.monotonic() >= deadline:
+                            return
+                        # the queue stays empty now: this is the 0.5 s tick
+                        watch.next(timeout=0.5)
+                        if writer.dead:
+                            return
+                        if bookmarks:
+                            # under the lock, so the bookmark cannot overtake
+                            # an event at or below its resourceVersion
+                            with cluster._lock:
+                                rv = watch.bookmark_rv()
+                                if rv is not None and rv != last_bookmark:
+                                    last_bookmark = rv
+                                    writer.write(bookmark_line(rv))
+                                    continue
+                        # keep-alive probe surfaces dead clients
+                        writer.write(b"\n")
+                finally:
+                    watch.stop()  # under the cluster lock: no sink call after
+                    writer.close()
+                return
             try:
                 while not getattr(server, "_shutting_down", False):
                     if deadline is not None and time.monotonic() >= deadline:
@@ -660,12 +731,7 @@ def _make_threaded_server(host, port, cluster):
                             rv = watch.bookmark_rv()
                             if rv is not None and rv != last_bookmark:
                                 last_bookmark = rv
-                                self.wfile.write((json.dumps({
-                                    "type": "BOOKMARK",
-                                    "object": {"kind": kind,
-                                               "apiVersion": api_version,
-                                               "metadata": {"resourceVersion": rv}},
-                                }) + "\n").encode())
+                                self.wfile.write(bookmark_line(rv))
                                 self.wfile.flush()
                                 continue
                         # keep-alive probe surfaces dead clients

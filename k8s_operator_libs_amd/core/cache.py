@@ -42,6 +42,14 @@ class _Informer:
     #: LIST-then-WATCH(rv) automatically when the server rejects it.
     USE_WATCH_LIST = True
 
+    #: over a watch that offers ``drain_events`` (the REST client's
+    #: line-pump path) ``get``, ``list`` and ``wait_for_rv`` decode and apply
+    #: pending events on the calling thread, and the informer thread only
+    #: handles control: end of stream, in-stream ERROR, relist, backoff.
+    #: False (or a ``sync_delay``) routes every event through the informer
+    #: thread as before.
+    USE_DRAIN_ON_READ = True
+
     def __init__(self, delegate: Client, api_version: str, kind: str,
                  sync_delay: float = 0.0) -> None:
         self.api_version = api_version
@@ -60,6 +68,9 @@ class _Informer:
         # last resourceVersion this informer has processed: the anchor for
         # lossless watch reconnects (client-go reflector lastSyncResourceVersion)
         self._last_rv: Optional[str] = None
+        # ERROR events met while readers applied events: the informer
+        # thread picks them up at its next tick
+        self._control: list = []
 
     def start(self) -> None:
         self._thread = threading.Thread(target=self._run, daemon=True)
@@ -127,8 +138,6 @@ class _Informer:
         return False
 
     def _run(self) -> None:
-        from .errors import GoneError
-
         backoff = self.BACKOFF_BASE
         # reflector bootstrap: WatchList when available, else LIST (capture
         # list RV) -> WATCH(from that RV).  With an RV-anchored delegate
@@ -153,71 +162,120 @@ class _Informer:
         self._synced.set()
         backoff = self.BACKOFF_BASE
         while not self._stop.is_set():
-            item = self._watch.next(timeout=0.2)
-            if item is None:
-                alive = getattr(self._watch, "alive", None)
-                if alive is not None and not alive():
-                    # stream dropped: re-watch from the last processed RV —
-                    # only a 410 (resume window expired) forces a full relist
-                    self._watch.stop()
+            watch = self._watch
+            if self._reads_directly(watch):
+                # control only: readers apply the events themselves.  Wake
+                # at the tick or at the end of the stream, apply whatever
+                # nobody has read, then see to ERROR events and a drop.
+                watch.wait_ended(0.2)
+                with self._lock:
+                    self._apply_pending(watch)
+                    items, self._control = self._control, []
+                items.append(None)
+            else:
+                items = [watch.next(timeout=0.2)]
+            for item in items:
+                if self._watch is not watch:
+                    break  # re-watched: the rest belongs to the old stream
+                backoff = self._handle(item, backoff)
+
+    def _handle(self, item, backoff: float) -> float:
+        """One step of the informer thread: a watch event, or None for an
+        idle tick.  Returns the reconnect backoff to carry on with."""
+        from .errors import GoneError
+
+        if item is None:
+            alive = getattr(self._watch, "alive", None)
+            if alive is not None and not alive() and not self._stop.is_set():
+                # stream dropped: re-watch from the last processed RV —
+                # only a 410 (resume window expired) forces a full relist
+                if self._reads_directly(self._watch):
+                    with self._lock:  # its last lines, before it goes
+                        self._apply_pending(self._watch)
+                self._watch.stop()
+                try:
+                    self._set_watch(self._open_watch())
+                    if self._last_rv is None:
+                        self._relist()
+                    backoff = self.BACKOFF_BASE
+                except GoneError:
                     try:
-                        self._watch = self._open_watch()
-                        if self._last_rv is None:
-                            self._relist()
+                        self._relist()
+                        self._set_watch(self._open_watch())
                         backoff = self.BACKOFF_BASE
-                    except GoneError:
-                        try:
-                            self._relist()
-                            self._watch = self._open_watch()
-                            backoff = self.BACKOFF_BASE
-                        except Exception:
-                            self._stop.wait(backoff)
-                            backoff = min(backoff * 2, self.BACKOFF_MAX)
                     except Exception:
                         self._stop.wait(backoff)
                         backoff = min(backoff * 2, self.BACKOFF_MAX)
-                continue
-            event_type, obj = item
-            if event_type == "BOOKMARK":
-                rv = (obj or {}).get("metadata", {}).get("resourceVersion")
-                if rv:
-                    self._last_rv = rv
-                continue
-            if event_type == "ERROR":
-                # Kubernetes signals an expired watch as an in-stream ERROR
-                # Status (code 410): relist + re-watch from the fresh RV
-                code = (obj or {}).get("code")
-                try:
-                    if code == 410:
-                        self._relist()
-                    self._watch.stop()
-                    self._watch = self._open_watch()
                 except Exception:
                     self._stop.wait(backoff)
                     backoff = min(backoff * 2, self.BACKOFF_MAX)
-                continue
-            if self._sync_delay:
-                time.sleep(self._sync_delay)
-            key = (meta.namespace(obj), meta.name(obj))
-            with self._lock:
-                rv = meta.resource_version(obj)
-                if event_type == "DELETED":
-                    self._store.pop(key, None)
-                    self._last_rv = rv or self._last_rv
-                    self._changed.notify_all()
-                else:
-                    current = self._store.get(key)
-                    # resourceVersions are monotonic ints in this stack;
-                    # never regress the cache on out-of-order delivery
-                    if current is not None:
-                        try:
-                            if int(rv) < int(meta.resource_version(current)):
-                                continue
-                        except ValueError:
-                            pass
-                    self._store[key] = obj
-                    self._last_rv = rv or self._last_rv
-                    self._changed.notify_all()
+            return backoff
+        event_type, obj = item
+        if event_type == "ERROR":
+            # Kubernetes signals an expired watch as an in-stream ERROR
+            # Status (code 410): relist + re-watch from the fresh RV
+            code = (obj or {}).get("code")
+            try:
+                if code == 410:
+                    self._relist()
+                self._watch.stop()
+                self._set_watch(self._open_watch())
+            except Exception:
+                self._stop.wait(backoff)
+                backoff = min(backoff * 2, self.BACKOFF_MAX)
+            return backoff
+        if self._sync_delay and event_type != "BOOKMARK":
+            time.sleep(self._sync_delay)
+        with self._lock:
+            self._apply_event(event_type, obj)
+        return backoff
+
+    def _set_watch(self, watch) -> None:
+        with self._lock:
+            self._watch = watch
+            self._changed.notify_all()  # barriers move over to the new stream
+
+    def _reads_directly(self, watch) -> bool:
+        """True when readers take this watch's events themselves
+        (``drain_events`` on their own thread) and the informer thread is
+        no hop in the event path."""
+        return (self.USE_DRAIN_ON_READ and not self._sync_delay
+                and getattr(watch, "direct", False))
+
+    def _apply_pending(self, watch) -> None:
+        """Decode and apply every event ``watch`` has received and nobody
+        has read.  Called with the informer lock held."""
+        for event_type, obj in watch.drain_events():
+            self._apply_event(event_type, obj)
+
+    def _apply_event(self, event_type: str, obj) -> None:
+        """Apply one watch event to the store: the one place every path
+        goes through.  Called with the informer lock held."""
+        if event_type == "BOOKMARK":
+            rv = (obj or {}).get("metadata", {}).get("resourceVersion")
+            if rv:
+                self._last_rv = rv
+            return
+        if event_type == "ERROR":
+            self._control.append((event_type, obj))  # the informer thread's
+            return
+        key = (meta.namespace(obj), meta.name(obj))
+        rv = meta.resource_version(obj)
+        if event_type == "DELETED":
+            self._store.pop(key, None)
+        else:
+            current = self._store.get(key)
+            # resourceVersions are monotonic ints in this stack;
+            # never regress the cache on out-of-order delivery
+            if current is not None:
+                try:
+                    if int(rv) < int(meta.resource_version(current)):
+                        return
+                except ValueError:
+                    pass
+            self._store[key] = obj
+        self._last_rv = rv or self._last_rv
+        self._changed.notify_all()
 
     def stop(self) -> None:
         self._stop.set()
@@ -234,7 +292,9 @@ class _Informer:
         """Block until the cached copy of (namespace, name) has
         resourceVersion >= ``rv``, or the object is absent from the cache
         (deleted), or the timeout elapses.  Event-driven via the informer's
-        condition variable — no polling."""
+        condition variable — no polling.  Over a watch that hands out its
+        events directly the waiter applies them itself, woken by the native
+        reader thread, and the informer thread is not involved."""
         try:
             target = int(rv)
         except (TypeError, ValueError):
@@ -251,16 +311,31 @@ class _Informer:
             except ValueError:
                 return False
 
-        with self._changed:
-            while not caught_up():
+        while True:
+            with self._changed:
+                watch = self._watch
+                direct = self._reads_directly(watch)
+                if direct:
+                    seen = watch.seq()  # before the drain: no line is missed
+                    self._apply_pending(watch)
+                if caught_up():
+                    return True
                 remaining = deadline - time.monotonic()
                 if remaining <= 0:
                     return False
-                self._changed.wait(remaining)
-            return True
+                if not direct or watch.ended():
+                    # the informer thread applies events, or is about to
+                    # re-watch: either way it notifies
+                    self._changed.wait(remaining)
+                    continue
+            # woken by the native reader; the first waiter to take the lock
+            # applies the event for all of them
+            watch.wait_lines(seen, remaining)
 
     def get(self, name: str, namespace: str) -> K8sObject:
         with self._lock:
+            if self._reads_directly(self._watch):
+                self._apply_pending(self._watch)
             obj = self._store.get((namespace, name))
             if obj is None:
                 raise NotFoundError(f"{self.kind} {namespace}/{name} not found (cache)")
@@ -272,6 +347,8 @@ class _Informer:
         fsel = meta.parse_field_selector(field_selector)
         out = []
         with self._lock:
+            if self._reads_directly(self._watch):
+                self._apply_pending(self._watch)
             for (ns, _), obj in self._store.items():
                 if namespace not in (None, "") and ns != namespace:
                     continue

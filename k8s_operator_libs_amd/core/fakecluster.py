@@ -84,6 +84,7 @@ class Watch:
         # stops-matching -> DELETED transform); only used with selectors
         self._matched: set = set()
         self.events: "queue.Queue[Tuple[str, K8sObject]]" = queue.Queue()
+        self._sink: Optional[Callable[[str, K8sObject], None]] = None
         self._stopped = False
 
     def _matches(self, snapshot: K8sObject) -> bool:
@@ -115,7 +116,28 @@ class Watch:
                 event_type = "DELETED"
             else:
                 return
-        self.events.put((event_type, snapshot))
+        sink = self._sink
+        if sink is None:
+            self.events.put((event_type, snapshot))
+            return
+        try:
+            sink(event_type, snapshot)
+        except Exception:
+            # like a change hook: a failing consumer must never fail the
+            # API mutation that produced the event
+            logging.getLogger(__name__).exception(
+                "watch sink failed for %s %s", event_type, meta.name(snapshot)
+            )
+
+    def set_sink(
+        self, sink: Optional[Callable[[str, K8sObject], None]]
+    ) -> None:
+        """Hand every later event to ``sink(event_type, snapshot)`` instead of
+        the queue.  The sink runs on the mutating thread under the cluster
+        lock, so calls arrive in resourceVersion order; it must not block.
+        Install it while holding the cluster lock, after draining
+        ``events``, so that nothing is delivered in between."""
+        self._sink = sink
 
     def next(self, timeout: Optional[float] = None) -> Optional[Tuple[str, K8sObject]]:
         try:
@@ -127,7 +149,9 @@ class Watch:
         """Current cluster resourceVersion, but only when this watch's queue
         is drained — taken under the cluster lock so no event at or below the
         returned RV can still be pending delivery.  This makes the value safe
-        to hand out as a BOOKMARK a client may resume from."""
+        to hand out as a BOOKMARK a client may resume from.  With a sink
+        installed the queue is always empty and every such event has already
+        been handed to the sink, in order."""
         with self._cluster._lock:
             if not self.events.empty():
                 return None
@@ -160,6 +184,8 @@ class FakeCluster:
         self._kinds = dict(_BUILTIN_KINDS)
         self._watches: Dict[Tuple[str, str], List[Watch]] = {}
         self._change_hooks: List[Callable[[str, K8sObject], None]] = []
+        # (snapshot, {event_type: wire line}) of the event being delivered
+        self._line_cache: Optional[Tuple[K8sObject, Dict[str, bytes]]] = None
         # Watch-resume cache: per kind, a bounded deque of
         # (rv_int, event_type, snapshot).  Recording starts when the first
         # watch on the kind opens (before that, any RV-anchored resume gets
@@ -269,6 +295,7 @@ class FakeCluster:
                 pass
         for w in watches or ():
             w._deliver(event_type, snapshot)
+        self._line_cache = None
         for hook in self._change_hooks:
             # hooks are observers (simulated controllers): a failing hook
             # must never fail the API mutation that triggered it
@@ -278,6 +305,21 @@ class FakeCluster:
                 logging.getLogger(__name__).exception(
                     "change hook failed for %s %s", event_type, meta.name(obj)
                 )
+
+    def event_line(self, event_type: str, snapshot: K8sObject) -> bytes:
+        """The newline-terminated WatchEvent JSON of an event, for watch
+        sinks that write to a stream.  Called under the cluster lock.  While
+        one mutation is being delivered the line is built once per event
+        type (a selector watch may turn MODIFIED into ADDED or DELETED),
+        however many watches receive it."""
+        cache = self._line_cache
+        if cache is None or cache[0] is not snapshot:
+            cache = self._line_cache = (snapshot, {})
+        line = cache[1].get(event_type)
+        if line is None:
+            line = cache[1][event_type] = (json.dumps(
+                {"type": event_type, "object": snapshot}) + "\n").encode()
+        return line
 
     def _index_pod(self, obj: K8sObject, remove: bool = False) -> None:
         if meta.kind(obj) != "Pod":

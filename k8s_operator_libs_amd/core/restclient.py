@@ -17,6 +17,7 @@ Configuration resolution order (``from_environment``):
 
 from __future__ import annotations
 
+import collections
 import http.client as _http_client
 import json
 import os
@@ -533,7 +534,18 @@ class _HttpWatch:
     constructor returns once the response headers arrive (the server has
     registered the watch by then); against an RV-anchored server nothing can
     be lost before that because the informer resumes from its list RV.
-    ``ERROR`` and ``BOOKMARK`` events pass through to the consumer."""
+    ``ERROR`` and ``BOOKMARK`` events pass through to the consumer.
+
+    On plain-HTTP endpoints with the ``_wire`` extension there is no Python
+    reader thread and no queue: a ``_wire.LinePump`` thread collects the
+    lines without the GIL and :meth:`next` (wait, drain, ``json.loads``)
+    decodes them on the caller's thread.  A consumer that wants the events
+    on a thread of its own choosing takes them with :meth:`drain_events`
+    (see ``cache._Informer``)."""
+
+    #: read plain-HTTP streams with ``_wire.LinePump`` when the extension has
+    #: it; False keeps the Python reader thread over ``_wire.LineReader``
+    USE_LINE_PUMP = True
 
     def __init__(self, client: RestClient, api_version: str, kind: str,
                  namespace=None, resource_version=None,
@@ -661,16 +673,129 @@ class _HttpWatch:
                         pass
 
         self._sock = None
-        if client._wire is not None and client._fast_netloc is not None:
-            reader = native_reader
         self._resp = None
+        self._pump = None
+        # decoded events not yet handed out (line-pump path)
+        self._ready: "collections.deque" = collections.deque()
+        self._stop_lock = threading.Lock()
+        wire = client._wire
+        if wire is not None and client._fast_netloc is not None:
+            if self.USE_LINE_PUMP and hasattr(wire, "LinePump"):
+                self._open_pumped(client, wire, path, params)
+                if self._error is not None:
+                    raise self._error
+                return
+            reader = native_reader
         self._thread = threading.Thread(target=reader, daemon=True)
         self._thread.start()
         self._connected.wait(10.0)
         if self._error is not None:
             raise self._error
 
+    def _open_pumped(self, client, wire, path, params) -> None:
+        """Plain-HTTP endpoints with ``_wire.LinePump``: connect and read the
+        response head here, on the caller's thread; from then on a native
+        thread reads the lines and never takes the GIL."""
+        import urllib.parse
+
+        from .errors import GoneError
+
+        sock = None
+        try:
+            sock = client._wire_connect()
+            request = (
+                f"GET {path}?{urllib.parse.urlencode(params)} HTTP/1.1\r\n"
+            ).encode("latin-1") + client._wire_head() + b"\r\n"
+            sock.sendall(request)
+            # the reader stays the one place that frames the stream; the
+            # pump's thread reads through it
+            pump = wire.LinePump(wire.LineReader(sock.fileno()))
+        except Exception as exc:
+            self._pump_failed(sock, None, exc)
+            return
+        try:
+            status = pump.read_head(client._timeout)
+        except Exception as exc:
+            self._pump_failed(sock, pump, exc)
+            return
+        if status == 410 or status >= 400:
+            if status == 410:
+                self._error = GoneError("watch resume point expired")
+            else:
+                self._error = ApiError(f"watch rejected: HTTP {status}")
+                self._error.code = status
+            self._pump_failed(sock, pump, None)
+            return
+        self._sock = sock
+        self._pump = pump
+        self._thread = _PumpThread(pump)
+
+    def _pump_failed(self, sock, pump, exc) -> None:
+        """The stream never opened: like a stream that dropped at once,
+        ``alive()`` is False and the informer layer reconnects."""
+        import logging as _logging
+        import socket as _socket
+
+        if exc is not None:
+            _logging.getLogger(__name__).warning("watch stream ended: %s", exc)
+        if sock is not None:
+            try:
+                sock.shutdown(_socket.SHUT_RDWR)
+            except OSError:
+                pass
+        if pump is not None:
+            pump.stop()
+        if sock is not None:
+            sock.close()
+        self._stop.set()
+        self._thread = _PumpThread(None)
+
+    # -- line-pump path: lines are decoded on the thread that asks -------------
+
+    @property
+    def direct(self) -> bool:
+        """True when events can be taken with :meth:`drain_events` on the
+        consumer's own thread (the line-pump path)."""
+        return self._pump is not None
+
+    def seq(self) -> int:
+        """Lines received so far; pass it to :meth:`wait_lines`.  Read it
+        BEFORE :meth:`drain_events`, so a line that arrives in between ends
+        the wait at once and is never slept through."""
+        return self._pump.seq
+
+    def wait_lines(self, seen_seq: int, timeout: Optional[float]) -> int:
+        """Block (GIL released) until more than ``seen_seq`` lines have
+        arrived, the stream has ended, or the timeout is up."""
+        return self._pump.wait(seen_seq, timeout)
+
+    def wait_ended(self, timeout: Optional[float]) -> bool:
+        """Block until the stream has ended or the timeout is up."""
+        self._pump.wait(_NEVER_SEQ, timeout)
+        return self._pump.ended
+
+    def ended(self) -> bool:
+        return self._pump.ended
+
+    def lines_pending(self) -> int:
+        return self._pump.pending
+
+    def drain_events(self) -> list:
+        """Every event that has arrived and has not been handed out, oldest
+        first, decoded here.  One consumer at a time (with :meth:`next`)."""
+        out = list(self._ready)
+        self._ready.clear()
+        for line in self._pump.drain():
+            try:
+                event = json.loads(line)
+            except ValueError:
+                continue
+            out.append((event.get("type"), event.get("object")))
+        return out
+
     def next(self, timeout: Optional[float] = None):
+        if self._pump is not None:
+            return self._next_pumped(timeout)
         import queue
 
         try:
@@ -678,9 +803,46 @@ class _HttpWatch:
         except queue.Empty:
             return None
 
+    def _next_pumped(self, timeout: Optional[float]):
+        import time
+
+        deadline = None if timeout is None else time.monotonic() + timeout
+        ready = self._ready
+        while not ready:
+            seen = self._pump.seq
+            ready.extend(self.drain_events())
+            if ready:
+                break
+            remaining = None if deadline is None else deadline - time.monotonic()
+            if remaining is not None and remaining <= 0:
+                return None
+            if self._pump.ended:
+                if self._pump.pending:
+                    continue  # the last lines raced the end of the stream
+                # nothing will ever arrive: still honour the timeout, so a
+                # polling consumer does not spin on a dropped stream
+                self._stop.wait(remaining)
+                return None
+            self._pump.wait(seen, remaining)
+        return ready.popleft()
+
     def stop(self) -> None:
         self._stop.set()
         sock = self._sock
+        if self._pump is not None:
+            import socket
+
+            with self._stop_lock:
+                sock, self._sock = self._sock, None
+                if sock is None:
+                    return
+                try:
+                    sock.shutdown(socket.SHUT_RDWR)  # wakes the pump's thread
+                except OSError:
+                    pass
+                self._pump.stop()  # joined: the fd can no longer be in use
+                sock.close()
+            return
         if sock is not None:
             # wake the native reader; it closes the socket itself once it
             # has left readline
@@ -702,3 +864,23 @@ class _HttpWatch:
     def alive(self) -> bool:
         """False once the HTTP stream has ended (server drop or stop)."""
         return self._thread.is_alive() and not self._stop.is_set()
+
+
+#: a line count no stream reaches: LinePump.wait then returns only at the end
+#: of the stream or at its timeout
+_NEVER_SEQ = 2 ** 64 - 1
+
+
+class _PumpThread:
+    """``join`` / ``is_alive`` of ``threading.Thread`` over the native reader
+    thread of a ``_wire.LinePump`` (None: it never started)."""
+
+    def __init__(self, pump) -> None:
+        self._pump = pump
+
+    def is_alive(self) -> bool:
+        return self._pump is not None and not self._pump.ended
+
+    def join(self, timeout: Optional[float] = None) -> None:
+        if self._pump is not None:
+            self._pump.wait(_NEVER_SEQ, timeout)

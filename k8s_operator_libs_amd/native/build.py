@@ -19,6 +19,7 @@ JSONOPS_OUTPUT = os.path.join(PKG_DIR, "_jsonops.so")
 WIRE_SOURCES = (
     os.path.join(PKG_DIR, "wire.cpp"),
     os.path.join(PKG_DIR, "wire_core.hpp"),
+    os.path.join(PKG_DIR, "wire_stream.hpp"),
 )
 WIRE_OUTPUT = os.path.join(PKG_DIR, "_wire.so")
 
@@ -51,7 +52,7 @@ def build_jsonops(force: bool = False, verbose: bool = False) -> str:
 
 def build_wire(force: bool = False, verbose: bool = False) -> str:
     """Compile the native HTTP/1.1 wire path (plain C++, no ROCm); stale
-    when either wire.cpp or wire_core.hpp is newer than the .so."""
+    when wire.cpp or one of its headers is newer than the .so."""
     if (
         not force
         and os.path.exists(WIRE_OUTPUT)
@@ -60,7 +61,7 @@ def build_wire(force: bool = False, verbose: bool = False) -> str:
     ):
         return WIRE_OUTPUT
     cmd = [
-        CXX, "-O3", "-std=c++17", "-fPIC", "-shared",
+        CXX, "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread",
         f"-I{sysconfig.get_paths()['include']}",
         WIRE_SOURCES[0], "-o", WIRE_OUTPUT,
     ]

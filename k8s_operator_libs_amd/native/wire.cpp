@@ -13,24 +13,44 @@
 //   parse_request_head(data)          -> None | (method, target, ...)
 //     (the threaded apiserver's side of the same exchange)
 //
+// and carries a watch event from the write that caused it to the thread that
+// waits for it without a Python thread in between (docs/performance.md):
+//
+//   StreamWriter(fd, max_backlog).write(line) -> bool
+//       server side: the mutating thread sends the line itself; one native
+//       thread per process drains what a full socket left behind
+//   LinePump(fd | LineReader).wait(seen_seq, timeout) -> seq, .drain()
+//       client side: one native thread per stream reads head and lines
+//
 // Rules: the fd belongs to the Python socket object and is never closed
 // here; every wait is poll()+recv()/send() with the remaining deadline and
-// with the GIL released; EINTR re-takes the GIL and runs signal handlers.
-// Parsing lives in wire_core.hpp (no Python, no sockets).
+// with the GIL released; EINTR re-takes the GIL and runs signal handlers;
+// the native threads never take the GIL.  Parsing lives in wire_core.hpp,
+// backlog, line framing and the pending-line queue in wire_stream.hpp (no
+// Python, no sockets).
 
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
 
+#include <atomic>
 #include <cerrno>
 #include <chrono>
+#include <memory>
+#include <mutex>
 #include <new>
 #include <string>
+#include <system_error>
+#include <thread>
+#include <vector>
 
+#include <fcntl.h>
 #include <poll.h>
 #include <sys/socket.h>
 #include <sys/types.h>
+#include <unistd.h>
 
 #include "wire_core.hpp"
+#include "wire_stream.hpp"
 
 namespace {
 
@@ -361,24 +381,14 @@ PyObject* py_parse_request_head(PyObject* /*self*/, PyObject* arg) {
 struct LineReaderObject {
   PyObject_HEAD
   int fd;
-  bool busy;         // a call is inside poll/recv with the GIL released
-  bool head_done;
-  bool stream_end;   // body complete or peer closed
-  bool flushed;      // unterminated tail already handed out
-  int mode;          // 0 until-close, 1 chunked, 2 content-length
-  size_t remaining;  // mode 2
-  wire::HeadParser* head;
-  wire::ChunkedDecoder* chunked;
-  wire::LineSplitter* lines;
-  std::string* scratch;  // decoded chunk payload
-  std::string* buf;      // recv buffer
+  bool busy;  // a call is inside poll/recv with the GIL released, or a
+              // LinePump's thread reads through this reader
+  wire::LineFramer* framer;
+  std::string* buf;  // recv buffer
 };
 
 void linereader_dealloc(LineReaderObject* self) {
-  delete self->head;
-  delete self->chunked;
-  delete self->lines;
-  delete self->scratch;
+  delete self->framer;
   delete self->buf;
   Py_TYPE(self)->tp_free(reinterpret_cast<PyObject*>(self));
 }
@@ -386,22 +396,14 @@ void linereader_dealloc(LineReaderObject* self) {
 int linereader_init(LineReaderObject* self, PyObject* args, PyObject* /*kw*/) {
   int fd;
   if (!PyArg_ParseTuple(args, "i", &fd)) return -1;
-  if (self->head != nullptr) {
+  if (self->framer != nullptr) {
     PyErr_SetString(PyExc_RuntimeError, "LineReader is already initialised");
     return -1;
   }
   self->fd = fd;
   self->busy = false;
-  self->head_done = false;
-  self->stream_end = false;
-  self->flushed = false;
-  self->mode = 0;
-  self->remaining = 0;
   try {
-    self->head = new wire::HeadParser(wire::HeadParser::kResponse);
-    self->chunked = new wire::ChunkedDecoder();
-    self->lines = new wire::LineSplitter();
-    self->scratch = new std::string();
+    self->framer = new wire::LineFramer();
     self->buf = new std::string(kRecvBuf, '\0');
   } catch (const std::bad_alloc&) {
     PyErr_NoMemory();
@@ -410,64 +412,8 @@ int linereader_init(LineReaderObject* self, PyObject* args, PyObject* /*kw*/) {
   return 0;
 }
 
-// Route received bytes through head -> body framing -> line splitter.
-// Returns false with a Python exception set on malformed framing.
-bool linereader_consume(LineReaderObject* self, const char* p, size_t n) {
-  while (n > 0) {
-    size_t used = 0;
-    if (!self->head_done) {
-      int st = self->head->feed(p, n, &used);
-      if (st < 0) {
-        raise_wire_error(st);
-        return false;
-      }
-      if (st == wire::kDone) {
-        int code = self->head->status;
-        if (code >= 100 && code < 200 && code != 101) {
-          self->head->reset();
-        } else {
-          self->head_done = true;
-          if (status_has_no_body(code)) {
-            self->stream_end = true;
-          } else if (self->head->chunked) {
-            self->mode = 1;
-          } else if (self->head->has_content_length) {
-            self->mode = 2;
-            self->remaining = self->head->content_length;
-            if (self->remaining == 0) self->stream_end = true;
-          } else {
-            self->mode = 0;
-          }
-        }
-      }
-    } else if (self->stream_end) {
-      return true;  // bytes past the body are not ours
-    } else if (self->mode == 1) {
-      self->scratch->clear();
-      int st = self->chunked->feed(p, n, &used, self->scratch);
-      self->lines->feed(self->scratch->data(), self->scratch->size());
-      if (st < 0) {
-        raise_wire_error(st);
-        return false;
-      }
-      if (st == wire::kDone) self->stream_end = true;
-    } else if (self->mode == 2) {
-      used = n < self->remaining ? n : self->remaining;
-      self->lines->feed(p, used);
-      self->remaining -= used;
-      if (self->remaining == 0) self->stream_end = true;
-    } else {
-      used = n;
-      self->lines->feed(p, used);
-    }
-    p += used;
-    n -= used;
-  }
-  return true;
-}
-
-// One poll+recv round.  Returns kIoOk (bytes consumed or stream_end set),
-// kIoTimeout, or kIoError/kIoSignal with an exception set.
+// One poll+recv round.  Returns kIoOk (bytes consumed or the stream's end
+// noted), kIoTimeout, or kIoError/kIoSignal with an exception set.
 IoResult linereader_fill(LineReaderObject* self, const Deadline& dl) {
   size_t got = 0;
   self->busy = true;
@@ -476,11 +422,15 @@ IoResult linereader_fill(LineReaderObject* self, const Deadline& dl) {
   self->busy = false;
   if (io != kIoOk) return io;
   if (got == 0) {
-    self->stream_end = true;
+    self->framer->peer_closed();
     return kIoOk;
   }
   try {
-    if (!linereader_consume(self, self->buf->data(), got)) return kIoError;
+    int st = self->framer->consume(self->buf->data(), got);
+    if (st < 0) {
+      raise_wire_error(st);
+      return kIoError;
+    }
   } catch (const std::bad_alloc&) {
     PyErr_NoMemory();
     return kIoError;
@@ -489,7 +439,7 @@ IoResult linereader_fill(LineReaderObject* self, const Deadline& dl) {
 }
 
 bool linereader_enter(LineReaderObject* self) {
-  if (self->head == nullptr) {
+  if (self->framer == nullptr) {
     PyErr_SetString(PyExc_RuntimeError, "LineReader is not initialised");
     return false;
   }
@@ -508,8 +458,8 @@ PyObject* linereader_read_head_impl(LineReaderObject* self, PyObject* args) {
   double timeout_s;
   if (!parse_timeout(timeout_obj, &timeout_s)) return nullptr;
   Deadline dl(timeout_s);
-  while (!self->head_done) {
-    if (self->stream_end) {
+  while (!self->framer->head_done()) {
+    if (self->framer->stream_end()) {
       PyErr_SetString(PyExc_ConnectionResetError,
                       "peer closed the connection without a response");
       return nullptr;
@@ -518,7 +468,7 @@ PyObject* linereader_read_head_impl(LineReaderObject* self, PyObject* args) {
     if (io == kIoTimeout) return raise_timeout();
     if (io != kIoOk) return nullptr;
   }
-  return PyLong_FromLong(self->head->status);
+  return PyLong_FromLong(self->framer->status());
 }
 
 PyObject* linereader_readline_impl(LineReaderObject* self, PyObject* args) {
@@ -530,23 +480,15 @@ PyObject* linereader_readline_impl(LineReaderObject* self, PyObject* args) {
   Deadline dl(timeout_s);
   std::string line;
   for (;;) {
-    int st = self->lines->next(&line);
+    int st = self->framer->next(&line);
     if (st == wire::kDone)
       return PyBytes_FromStringAndSize(line.data(), Py_ssize_t(line.size()));
     if (st < 0) return raise_wire_error(st);
-    if (self->stream_end) {
-      if (!self->head_done) {
+    if (self->framer->stream_end()) {
+      if (!self->framer->head_done()) {
         PyErr_SetString(PyExc_ConnectionResetError,
                         "peer closed the connection without a response");
         return nullptr;
-      }
-      if (!self->flushed) {
-        self->flushed = true;
-        st = self->lines->flush(&line);
-        if (st == wire::kDone)
-          return PyBytes_FromStringAndSize(line.data(),
-                                           Py_ssize_t(line.size()));
-        if (st < 0) return raise_wire_error(st);
       }
       PyErr_SetString(PyExc_EOFError, "stream ended");
       return nullptr;
@@ -577,13 +519,13 @@ PyObject* linereader_readline(LineReaderObject* self, PyObject* args) {
 }
 
 PyObject* linereader_get_status(LineReaderObject* self, void*) {
-  if (self->head == nullptr || !self->head_done) Py_RETURN_NONE;
-  return PyLong_FromLong(self->head->status);
+  if (self->framer == nullptr || !self->framer->head_done()) Py_RETURN_NONE;
+  return PyLong_FromLong(self->framer->status());
 }
 
 PyObject* linereader_get_chunked(LineReaderObject* self, void*) {
-  if (self->head == nullptr || !self->head_done) Py_RETURN_NONE;
-  return PyBool_FromLong(self->mode == 1);
+  if (self->framer == nullptr || !self->framer->head_done()) Py_RETURN_NONE;
+  return PyBool_FromLong(self->framer->chunked());
 }
 
 PyMethodDef linereader_methods[] = {
@@ -612,6 +554,573 @@ PyTypeObject LineReaderType = {
     PyVarObject_HEAD_INIT(nullptr, 0)
     "_wire.LineReader",           /* tp_name */
     sizeof(LineReaderObject),     /* tp_basicsize */
+};
+
+// ---------------------------------------------------------------------------
+// LinePump (client side of a watch stream)
+// ---------------------------------------------------------------------------
+
+// What the pump's thread works on.  The framer and the recv buffer belong
+// to the LineReader the pump holds a reference to; the thread is joined
+// before that reference is dropped.
+struct PumpState {
+  int fd = -1;
+  int wake[2] = {-1, -1};  // stop() writes, the thread polls the read end
+  wire::LineFramer* framer = nullptr;
+  std::string* buf = nullptr;
+  wire::LineQueue queue;
+};
+
+// The reader thread: head, then lines, into the queue.  Never takes the GIL.
+void pump_run(PumpState* st) {
+  int error = 0;
+  bool head_published = false;
+  try {
+    std::string line;
+    for (;;) {
+      struct pollfd p[2] = {{st->fd, POLLIN, 0}, {st->wake[0], POLLIN, 0}};
+      if (poll(p, 2, -1) < 0) {
+        if (errno == EINTR) continue;
+        error = errno;
+        break;
+      }
+      if (p[1].revents) break;  // stop()
+      ssize_t n = recv(st->fd, &(*st->buf)[0], st->buf->size(), MSG_DONTWAIT);
+      if (n < 0) {
+        if (errno == EAGAIN || errno == EWOULDBLOCK || errno == EINTR) continue;
+        error = errno;
+        break;
+      }
+      int bad = 0;
+      if (n == 0) {
+        st->framer->peer_closed();
+      } else {
+        bad = st->framer->consume(st->buf->data(), size_t(n));
+      }
+      // what arrived whole before a framing error is still handed out
+      if (!head_published && st->framer->head_done()) {
+        st->queue.set_head(st->framer->status());
+        head_published = true;
+      }
+      int rc;
+      while ((rc = st->framer->next(&line)) == wire::kDone)
+        st->queue.push(std::move(line));
+      if (bad < 0 || rc < 0) {
+        error = bad < 0 ? bad : rc;
+        break;
+      }
+      if (st->framer->stream_end()) break;
+    }
+  } catch (const std::bad_alloc&) {
+    error = ENOMEM;
+  }
+  st->queue.end(error);  // the thread's last use of the fd is behind it
+}
+
+struct LinePumpObject {
+  PyObject_HEAD
+  PyObject* reader;  // the LineReader whose framing state the thread drives
+  PumpState* st;
+  std::thread* thread;
+  bool joined;
+};
+
+// seen_seq that no stream reaches: wait() then returns only at the end of
+// the stream or at the timeout
+constexpr unsigned long long kNeverSeq = ~0ULL;
+
+void linepump_join(LinePumpObject* self, bool release_gil) {
+  if (self->thread == nullptr) return;
+  if (self->joined) {
+    // another caller is joining, or has: the queue's end is the thread's
+    // last act, so waiting for it is as good
+    if (release_gil) {
+      Py_BEGIN_ALLOW_THREADS
+      self->st->queue.wait(kNeverSeq, -1.0);
+      Py_END_ALLOW_THREADS
+    } else {
+      self->st->queue.wait(kNeverSeq, -1.0);
+    }
+    return;
+  }
+  self->joined = true;
+  char c = 0;
+  ssize_t rc = write(self->st->wake[1], &c, 1);
+  (void)rc;
+  if (release_gil) {
+    Py_BEGIN_ALLOW_THREADS
+    self->thread->join();
+    Py_END_ALLOW_THREADS
+  } else {
+    self->thread->join();
+  }
+}
+
+void linepump_dealloc(LinePumpObject* self) {
+  if (self->st != nullptr) {
+    linepump_join(self, false);
+    delete self->thread;
+    if (self->st->wake[0] >= 0) close(self->st->wake[0]);
+    if (self->st->wake[1] >= 0) close(self->st->wake[1]);
+    delete self->st;
+  }
+  Py_XDECREF(self->reader);
+  Py_TYPE(self)->tp_free(reinterpret_cast<PyObject*>(self));
+}
+
+int linepump_init(LinePumpObject* self, PyObject* args, PyObject* /*kw*/) {
+  PyObject* source;
+  if (!PyArg_ParseTuple(args, "O", &source)) return -1;
+  if (self->st != nullptr) {
+    PyErr_SetString(PyExc_RuntimeError, "LinePump is already initialised");
+    return -1;
+  }
+  PyObject* reader;
+  if (PyObject_TypeCheck(source, &LineReaderType)) {
+    reader = source;
+    Py_INCREF(reader);
+  } else {
+    reader = PyObject_CallFunctionObjArgs(
+        reinterpret_cast<PyObject*>(&LineReaderType), source, nullptr);
+    if (reader == nullptr) return -1;
+  }
+  LineReaderObject* lr = reinterpret_cast<LineReaderObject*>(reader);
+  if (!linereader_enter(lr)) {
+    Py_DECREF(reader);
+    return -1;
+  }
+  PumpState* st = nullptr;
+  try {
+    st = new PumpState();
+    st->fd = lr->fd;
+    st->framer = lr->framer;
+    st->buf = lr->buf;
+    if (pipe2(st->wake, O_NONBLOCK | O_CLOEXEC) != 0) {
+      PyErr_SetFromErrno(PyExc_OSError);
+      delete st;
+      Py_DECREF(reader);
+      return -1;
+    }
+    lr->busy = true;  // for good: the reader is the thread's from now on
+    self->reader = reader;
+    self->st = st;
+    self->joined = false;
+    self->thread = new std::thread(pump_run, st);
+  } catch (const std::exception&) {  // bad_alloc, or no thread to be had
+    if (self->st == nullptr) {
+      delete st;
+      Py_DECREF(reader);
+    } else {
+      st->queue.end(EAGAIN);  // dealloc tidies up; nothing was started
+    }
+    PyErr_SetString(PyExc_RuntimeError, "LinePump could not start its thread");
+    return -1;
+  }
+  return 0;
+}
+
+bool linepump_enter(LinePumpObject* self) {
+  if (self->st == nullptr) {
+    PyErr_SetString(PyExc_RuntimeError, "LinePump is not initialised");
+    return false;
+  }
+  return true;
+}
+
+// Run `step(seconds)` (GIL released) in slices of at most a second until
+// `done()` or the deadline, looking for signals in between.  False with an
+// exception set when a signal handler raised.
+template <class Step, class Done>
+bool linepump_wait_sliced(double timeout_s, Step step, Done done) {
+  Deadline dl(timeout_s);
+  for (;;) {
+    int ms = dl.remaining_ms();
+    double slice = ms < 0 || ms > 1000 ? 1.0 : double(ms) / 1000.0;
+    Py_BEGIN_ALLOW_THREADS
+    step(slice);
+    Py_END_ALLOW_THREADS
+    if (done() || dl.remaining_ms() == 0) return true;
+    if (PyErr_CheckSignals() < 0) return false;
+  }
+}
+
+PyObject* linepump_read_head(LinePumpObject* self, PyObject* args) {
+  PyObject* timeout_obj = Py_None;
+  if (!PyArg_ParseTuple(args, "|O", &timeout_obj)) return nullptr;
+  if (!linepump_enter(self)) return nullptr;
+  double timeout_s;
+  if (!parse_timeout(timeout_obj, &timeout_s)) return nullptr;
+  wire::LineQueue& q = self->st->queue;
+  int status = 0;
+  if (!linepump_wait_sliced(
+          timeout_s, [&](double s) { status = q.wait_head(s); },
+          [&] { return status != 0 || q.ended(); }))
+    return nullptr;
+  if (status != 0) return PyLong_FromLong(status);
+  if (!q.ended()) return raise_timeout();
+  int error = q.error();
+  if (error < 0) return raise_wire_error(error);
+  if (error > 0) {
+    errno = error;
+    return PyErr_SetFromErrno(PyExc_OSError);
+  }
+  PyErr_SetString(PyExc_ConnectionResetError,
+                  "peer closed the connection without a response");
+  return nullptr;
+}
+
+PyObject* linepump_wait(LinePumpObject* self, PyObject* args) {
+  unsigned long long seen;
+  PyObject* timeout_obj = Py_None;
+  if (!PyArg_ParseTuple(args, "K|O", &seen, &timeout_obj)) return nullptr;
+  if (!linepump_enter(self)) return nullptr;
+  double timeout_s;
+  if (!parse_timeout(timeout_obj, &timeout_s)) return nullptr;
+  wire::LineQueue& q = self->st->queue;
+  uint64_t seq = 0;
+  if (!linepump_wait_sliced(
+          timeout_s, [&](double s) { seq = q.wait(seen, s); },
+          [&] { return seq > seen || q.ended(); }))
+    return nullptr;
+  return PyLong_FromUnsignedLongLong(seq);
+}
+
+PyObject* linepump_drain(LinePumpObject* self, PyObject*) {
+  if (!linepump_enter(self)) return nullptr;
+  try {
+    std::deque<std::string> lines = self->st->queue.drain();
+    PyObject* out = PyList_New(Py_ssize_t(lines.size()));
+    if (!out) return nullptr;
+    Py_ssize_t i = 0;
+    for (const std::string& line : lines) {
+      PyObject* b =
+          PyBytes_FromStringAndSize(line.data(), Py_ssize_t(line.size()));
+      if (!b) {
+        Py_DECREF(out);
+        return nullptr;
+      }
+      PyList_SET_ITEM(out, i++, b);
+    }
+    return out;
+  } catch (const std::bad_alloc&) {
+    return PyErr_NoMemory();
+  }
+}
+
+PyObject* linepump_stop(LinePumpObject* self, PyObject*) {
+  if (!linepump_enter(self)) return nullptr;
+  linepump_join(self, true);
+  Py_RETURN_NONE;
+}
+
+PyObject* linepump_get_seq(LinePumpObject* self, void*) {
+  if (!linepump_enter(self)) return nullptr;
+  return PyLong_FromUnsignedLongLong(self->st->queue.seq());
+}
+
+PyObject* linepump_get_pending(LinePumpObject* self, void*) {
+  if (!linepump_enter(self)) return nullptr;
+  return PyLong_FromSize_t(self->st->queue.pending());
+}
+
+PyObject* linepump_get_ended(LinePumpObject* self, void*) {
+  if (!linepump_enter(self)) return nullptr;
+  return PyBool_FromLong(self->st->queue.ended());
+}
+
+PyObject* linepump_get_error(LinePumpObject* self, void*) {
+  if (!linepump_enter(self)) return nullptr;
+  int error = self->st->queue.error();
+  if (error == 0) Py_RETURN_NONE;
+  return PyUnicode_FromString(error < 0 ? wire::status_message(error)
+                                        : std::strerror(error));
+}
+
+PyMethodDef linepump_methods[] = {
+    {"read_head", reinterpret_cast<PyCFunction>(linepump_read_head),
+     METH_VARARGS,
+     "read_head(timeout=None) -> status.  Wait for the response head; "
+     "TimeoutError on deadline, ConnectionResetError, OSError or ValueError "
+     "when the stream ended before it."},
+    {"wait", reinterpret_cast<PyCFunction>(linepump_wait), METH_VARARGS,
+     "wait(seen_seq, timeout=None) -> seq.  Return once more than seen_seq "
+     "lines have arrived, the stream has ended, or the timeout is up.  The "
+     "GIL is released while waiting; every waiter is woken."},
+    {"drain", reinterpret_cast<PyCFunction>(linepump_drain), METH_NOARGS,
+     "drain() -> list[bytes].  Every pending line, oldest first."},
+    {"stop", reinterpret_cast<PyCFunction>(linepump_stop), METH_NOARGS,
+     "stop().  End the reader thread and join it (GIL released).  On return "
+     "nothing native uses the fd any more: close the socket only now."},
+    {nullptr, nullptr, 0, nullptr},
+};
+
+PyGetSetDef linepump_getset[] = {
+    {"seq", reinterpret_cast<getter>(linepump_get_seq), nullptr,
+     "lines received so far", nullptr},
+    {"pending", reinterpret_cast<getter>(linepump_get_pending), nullptr,
+     "lines received and not yet drained", nullptr},
+    {"ended", reinterpret_cast<getter>(linepump_get_ended), nullptr,
+     "True once the stream is over: body complete, peer closed, framing "
+     "error, read error or stop()", nullptr},
+    {"error", reinterpret_cast<getter>(linepump_get_error), nullptr,
+     "why the stream ended, None for a clean end", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+
+PyTypeObject LinePumpType = {
+    PyVarObject_HEAD_INIT(nullptr, 0)
+    "_wire.LinePump",             /* tp_name */
+    sizeof(LinePumpObject),       /* tp_basicsize */
+};
+
+// ---------------------------------------------------------------------------
+// StreamWriter (server side of a watch stream)
+// ---------------------------------------------------------------------------
+
+// One stream's fd and backlog, shared between its StreamWriter and the
+// flusher so that neither can outlive the other's use of it.
+struct Stream {
+  Stream(int fd_, size_t max_backlog) : fd(fd_), buf(max_backlog) {}
+
+  long send_some(const char* p, size_t n) const {
+    for (;;) {
+      ssize_t rc = send(fd, p, n, MSG_DONTWAIT | MSG_NOSIGNAL);
+      if (rc >= 0) return long(rc);
+      if (errno == EINTR) continue;
+      if (errno == EAGAIN || errno == EWOULDBLOCK) return wire::kSendWouldBlock;
+      return wire::kSendFailed;
+    }
+  }
+
+  // the peer learns of a dead stream at once; the fd itself stays open
+  void on_dead() {
+    if (!shut.exchange(true)) shutdown(fd, SHUT_RDWR);
+  }
+
+  const int fd;
+  wire::StreamBuffer buf;
+  std::atomic<bool> shut{false};
+};
+
+// The process's one flusher thread: drains backlogs when their sockets
+// report POLLOUT.  It never touches Python.  `mu_` is held across a flush
+// and across detach(), so once detach() has returned the thread does not
+// use that stream's fd again.
+class Flusher {
+ public:
+  static Flusher& instance() {
+    static Flusher* self = new Flusher();  // never destroyed: no exit races
+    return *self;
+  }
+
+  // `s` has a backlog: watch its fd from now on
+  bool attach(const std::shared_ptr<Stream>& s) {
+    std::lock_guard<std::mutex> hold(mu_);
+    if (!ensure_started()) return false;
+    for (const auto& have : active_)
+      if (have == s) return true;
+    active_.push_back(s);
+    wake();
+    return true;
+  }
+
+  void detach(const std::shared_ptr<Stream>& s) {
+    std::lock_guard<std::mutex> hold(mu_);
+    for (size_t i = 0; i < active_.size(); ++i) {
+      if (active_[i] == s) {
+        active_.erase(active_.begin() + long(i));
+        wake();
+        break;
+      }
+    }
+  }
+
+ private:
+  Flusher() = default;
+
+  bool ensure_started() {  // mu_ held
+    if (started_) return true;
+    if (pipe2(wake_, O_NONBLOCK | O_CLOEXEC) != 0) return false;
+    try {
+      std::thread(&Flusher::run, this).detach();
+    } catch (const std::system_error&) {
+      close(wake_[0]);
+      close(wake_[1]);
+      return false;
+    }
+    started_ = true;
+    return true;
+  }
+
+  void wake() {
+    char c = 0;
+    ssize_t rc = write(wake_[1], &c, 1);  // a full pipe is already a wake-up
+    (void)rc;
+  }
+
+  void run() {
+    std::vector<std::shared_ptr<Stream>> watched;
+    std::vector<struct pollfd> fds;
+    for (;;) {
+      {
+        std::lock_guard<std::mutex> hold(mu_);
+        watched = active_;
+      }
+      fds.clear();
+      fds.push_back({wake_[0], POLLIN, 0});
+      for (const auto& s : watched) fds.push_back({s->fd, POLLOUT, 0});
+      if (poll(fds.data(), nfds_t(fds.size()), -1) < 0) continue;  // EINTR
+      if (fds[0].revents) {
+        char sink[64];
+        while (read(wake_[0], sink, sizeof sink) > 0) {
+        }
+      }
+      for (size_t i = 0; i < watched.size(); ++i) {
+        if (!fds[i + 1].revents) continue;
+        const std::shared_ptr<Stream>& s = watched[i];
+        std::lock_guard<std::mutex> hold(mu_);
+        size_t at = 0;
+        while (at < active_.size() && active_[at] != s) ++at;
+        if (at == active_.size()) continue;  // detached while we polled
+        Stream* raw = s.get();
+        auto st = raw->buf.flush(
+            [raw](const char* p, size_t n) { return raw->send_some(p, n); });
+        if (st == wire::StreamBuffer::kQueued) continue;
+        if (st == wire::StreamBuffer::kDead) raw->on_dead();
+        active_.erase(active_.begin() + long(at));
+      }
+    }
+  }
+
+  std::mutex mu_;
+  std::vector<std::shared_ptr<Stream>> active_;
+  bool started_ = false;
+  int wake_[2] = {-1, -1};
+};
+
+// Default backlog cap: 64 MiB.  The replay that opens a watch (resume
+// history or the initial events of a whole kind) is written in one go under
+// the cluster lock and has to fit; 64 MiB is also the cap on a single line
+// (wire::kMaxLine), so no legal stream is refused for its first line.  A
+// reader that falls further behind than that is cut off and re-watches.
+constexpr size_t kDefaultMaxBacklog = wire::kMaxLine;
+
+struct StreamWriterObject {
+  PyObject_HEAD
+  std::shared_ptr<Stream>* stream;
+  bool closed;
+};
+
+void streamwriter_dealloc(StreamWriterObject* self) {
+  if (self->stream != nullptr) {
+    if (!self->closed) Flusher::instance().detach(*self->stream);
+    delete self->stream;
+  }
+  Py_TYPE(self)->tp_free(reinterpret_cast<PyObject*>(self));
+}
+
+int streamwriter_init(StreamWriterObject* self, PyObject* args,
+                      PyObject* /*kw*/) {
+  int fd;
+  Py_ssize_t max_backlog = Py_ssize_t(kDefaultMaxBacklog);
+  if (!PyArg_ParseTuple(args, "i|n", &fd, &max_backlog)) return -1;
+  if (self->stream != nullptr) {
+    PyErr_SetString(PyExc_RuntimeError, "StreamWriter is already initialised");
+    return -1;
+  }
+  if (fd < 0 || max_backlog < 0) {
+    PyErr_SetString(PyExc_ValueError, "fd and max_backlog must be >= 0");
+    return -1;
+  }
+  try {
+    self->stream = new std::shared_ptr<Stream>(
+        std::make_shared<Stream>(fd, size_t(max_backlog)));
+  } catch (const std::bad_alloc&) {
+    PyErr_NoMemory();
+    return -1;
+  }
+  self->closed = false;
+  return 0;
+}
+
+// Never raises for a stream that cannot take the data: the caller is a
+// cluster mutation that must go through whatever its watchers do.
+PyObject* streamwriter_write(StreamWriterObject* self, PyObject* arg) {
+  if (self->stream == nullptr) {
+    PyErr_SetString(PyExc_RuntimeError, "StreamWriter is not initialised");
+    return nullptr;
+  }
+  Py_buffer view;
+  if (PyObject_GetBuffer(arg, &view, PyBUF_SIMPLE) < 0) return nullptr;
+  bool ok = false;
+  if (!self->closed) {
+    const std::shared_ptr<Stream>& s = *self->stream;
+    Stream* raw = s.get();
+    try {
+      // send() is non-blocking, so the GIL stays held: releasing it would
+      // invite the thread switch this path exists to avoid
+      auto st = raw->buf.write(
+          static_cast<const char*>(view.buf), size_t(view.len),
+          [raw](const char* p, size_t n) { return raw->send_some(p, n); });
+      if (st == wire::StreamBuffer::kQueued && !Flusher::instance().attach(s)) {
+        raw->buf.kill();  // no flusher thread: the backlog would never drain
+        st = wire::StreamBuffer::kDead;
+      }
+      if (st == wire::StreamBuffer::kDead) raw->on_dead();
+      ok = st != wire::StreamBuffer::kDead;
+    } catch (const std::bad_alloc&) {
+      raw->buf.kill();
+      raw->on_dead();
+    }
+  }
+  PyBuffer_Release(&view);
+  return PyBool_FromLong(ok);
+}
+
+PyObject* streamwriter_close(StreamWriterObject* self, PyObject*) {
+  if (self->stream != nullptr && !self->closed) {
+    self->closed = true;
+    Flusher::instance().detach(*self->stream);
+  }
+  Py_RETURN_NONE;
+}
+
+PyObject* streamwriter_get_dead(StreamWriterObject* self, void*) {
+  if (self->stream == nullptr) Py_RETURN_TRUE;
+  return PyBool_FromLong(self->closed || (*self->stream)->buf.dead());
+}
+
+PyObject* streamwriter_get_pending(StreamWriterObject* self, void*) {
+  if (self->stream == nullptr) return PyLong_FromLong(0);
+  return PyLong_FromSize_t((*self->stream)->buf.pending());
+}
+
+PyMethodDef streamwriter_methods[] = {
+    {"write", reinterpret_cast<PyCFunction>(streamwriter_write), METH_O,
+     "write(data) -> bool.  Thread-safe, never blocks, never raises for a "
+     "broken stream.  With nothing queued the bytes are sent on the calling "
+     "thread; what the socket does not take waits in the backlog, which one "
+     "native thread per process drains on POLLOUT.  Each call's bytes reach "
+     "the peer contiguously.  False once the writer is dead or closed."},
+    {"close", reinterpret_cast<PyCFunction>(streamwriter_close), METH_NOARGS,
+     "close().  Detach from the flusher thread; on return nothing native "
+     "uses the fd any more.  Unsent backlog is dropped."},
+    {nullptr, nullptr, 0, nullptr},
+};
+
+PyGetSetDef streamwriter_getset[] = {
+    {"dead", reinterpret_cast<getter>(streamwriter_get_dead), nullptr,
+     "True after a send error, a backlog past max_backlog (the socket is "
+     "then shut down, not closed) or close()", nullptr},
+    {"pending", reinterpret_cast<getter>(streamwriter_get_pending), nullptr,
+     "bytes waiting in the backlog", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+
+PyTypeObject StreamWriterType = {
+    PyVarObject_HEAD_INIT(nullptr, 0)
+    "_wire.StreamWriter",         /* tp_name */
+    sizeof(StreamWriterObject),   /* tp_basicsize */
 };
 
 // ---------------------------------------------------------------------------
@@ -668,8 +1177,50 @@ PyMODINIT_FUNC PyInit__wire(void) {
   LineReaderType.tp_methods = linereader_methods;
   LineReaderType.tp_getset = linereader_getset;
   if (PyType_Ready(&LineReaderType) < 0) return nullptr;
+  StreamWriterType.tp_flags = Py_TPFLAGS_DEFAULT;
+  StreamWriterType.tp_doc =
+      "StreamWriter(fd, max_backlog=64 MiB): non-blocking, thread-safe line "
+      "writer over a socket the caller owns (never closed here).  The "
+      "default cap holds the replay that opens a watch, which is written in "
+      "one go, and equals the 64 MiB cap on a single line; a reader further "
+      "behind than that is cut off and re-watches.";
+  StreamWriterType.tp_new = PyType_GenericNew;
+  StreamWriterType.tp_init = reinterpret_cast<initproc>(streamwriter_init);
+  StreamWriterType.tp_dealloc =
+      reinterpret_cast<destructor>(streamwriter_dealloc);
+  StreamWriterType.tp_methods = streamwriter_methods;
+  StreamWriterType.tp_getset = streamwriter_getset;
+  if (PyType_Ready(&StreamWriterType) < 0) return nullptr;
+  LinePumpType.tp_flags = Py_TPFLAGS_DEFAULT;
+  LinePumpType.tp_doc =
+      "LinePump(fd | LineReader): one native thread reads the response head "
+      "and then lines from a socket the caller owns, without ever taking "
+      "the GIL; consumers wait() for the line count to move and drain().  "
+      "Given a LineReader, the thread reads through it and the reader is "
+      "the pump's from then on.  To end it: shut the socket down, stop(), "
+      "and only then close the socket.";
+  LinePumpType.tp_new = PyType_GenericNew;
+  LinePumpType.tp_init = reinterpret_cast<initproc>(linepump_init);
+  LinePumpType.tp_dealloc = reinterpret_cast<destructor>(linepump_dealloc);
+  LinePumpType.tp_methods = linepump_methods;
+  LinePumpType.tp_getset = linepump_getset;
+  if (PyType_Ready(&LinePumpType) < 0) return nullptr;
   PyObject* m = PyModule_Create(&wire_module);
   if (!m) return nullptr;
+  Py_INCREF(&LinePumpType);
+  if (PyModule_AddObject(m, "LinePump",
+                         reinterpret_cast<PyObject*>(&LinePumpType)) < 0) {
+    Py_DECREF(&LinePumpType);
+    Py_DECREF(m);
+    return nullptr;
+  }
+  Py_INCREF(&StreamWriterType);
+  if (PyModule_AddObject(m, "StreamWriter",
+                         reinterpret_cast<PyObject*>(&StreamWriterType)) < 0) {
+    Py_DECREF(&StreamWriterType);
+    Py_DECREF(m);
+    return nullptr;
+  }
   Py_INCREF(&LineReaderType);
   if (PyModule_AddObject(m, "LineReader",
                          reinterpret_cast<PyObject*>(&LineReaderType)) < 0) {
