@@ -27,6 +27,10 @@
 //                           attributed per unit (opt-in sweep)
 //   mx_mfma_tile()        — one scaled MFMA, raw codes + GPU tile returned
 //   mx_throughput_tflops() — sustained e2m1 / e4m3 MX burn-in
+//   xcd_fabric_check()    — hand-offs between workgroups on different XCDs
+//                           (agent-scope release, ticket, acquire) and every
+//                           device-scope atomic, exact, attributed per
+//                           (writer, reader) XCC pair (opt-in)
 //
 // Built standalone with hipcc (no torch linkage) via pybind11; the .so lives
 // in-tree so it travels to GPU nodes with the package.
@@ -2127,8 +2131,953 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Cross-XCD hand-off and device-scope atomics check.  The eight XCDs' L2s are
+// not coherent with each other: a word written on one XCD reaches a reader on
+// another only through an agent-scope release on the writer (L2 write-back),
+// an agent-scope acquire on the reader (L1 invalidate) and the memory-side
+// atomics between them.  Two kernels exercise exactly that path; every
+// workgroup does a fixed amount of work and exits, nobody waits for anybody.
+//
+// Hand-off sweep (xcd_handoff_kernel): the wait-free last-arriver protocol of
+// a split-K reduction with a pattern in place of partial sums.  group x G
+// workgroups; block b is member b / G of group b % G.  A 128-byte line is 16
+// 64-bit words: words 0-7 are static (host-filled once with
+// hash(seed ^ kXfStaticKey, idx), never written again), words 8-15 carry the
+// payload hash(seed + round, idx); idx is the word's index in the slab buffer
+// [reps][blocks][slab_lines][16].  Per rep a block
+//   1. reads and verifies the static halves of every line of its group's slabs
+//      (a real check that also leaves every line in this CU's L1 and this
+//      XCD's L2, so a later acquire has something to invalidate),
+//   2. writes the payload halves of its own slab and its XCC_ID,
+//   3. drains, releases at agent scope and draws a ticket,
+//   4. and, if it drew group - 1, acquires at agent scope and verifies every
+//      payload half of the group exactly.
+// The payload is not reset between rounds: what a broken hand-off reads is
+// the previous round's hash(seed + round - 1, idx); the upload is round -1.
+//
+// Which member arrives last decides the reader XCC of an episode.  Left to
+// the dispatcher that is heavily skewed: in a given launch the same few XCDs
+// arrive last in almost every group (measured: one XCC was the reader in 0 of
+// 1984 episodes of a run), and pairs stay uncovered for many rounds.  So
+// member (rep + round) % group of every episode idles for a fixed few
+// microseconds before it draws its ticket and every other member idles as
+// long after drawing its own: each block spends the same time per rep, and
+// the late member, and with it the reader XCC, rotates through the group.
+// This is a fixed delay, not a wait on anybody, and like the odd G it only
+// speeds coverage up: the verdict counts what happened and never relies on it.
+//
+// A (writer, reader) pair can only occur inside a group, and a group of fewer
+// members than there are XCCs (or a grid of a handful of blocks) never spans
+// them all.  So before its acquire a reducer looks once, with a compare-and-
+// swap that changes nothing, at the previous repetition's ticket counter of
+// up to kXfExtraGroups neighbour groups.  A counter that already holds all
+// its tickets proves that every member of that episode has released its slab,
+// so the reducer's acquire covers those slabs too and it verifies them as
+// well; a counter that does not is left alone.  One look, no loop.  These
+// extra lines are counted apart (no number of them is expected, so
+// lines_verified == lines_expected keeps its meaning) and count towards
+// pair coverage; their mismatches are errors like any other.
+//
+// Atomics sweep (xcd_atomics_kernel): 2 x CUs workgroups add, max, min, xor,
+// or and and hash-derived values into `cells` 128-byte lines at agent scope,
+// draw one ticket each from a single counter and contend once for a CAS
+// claim.  Every total is recomputed on the host with the same generator; the
+// f32 operands are integers with a per-cell sum of magnitudes of at most 2^23,
+// enforced by the generator, so every order of addition is exact.
+//
+// Counted, not trusted: ticket counters, episodes, verified words and tickets
+// are all counted on the device and compared on the host.  Every index that
+// derives from a returned atomic is range-checked before it is an address.
+// The poison hook is data only: it XORs bit 0 into the *expected* value.
+// ---------------------------------------------------------------------------
+
+constexpr int kXfBlock = 256;
+constexpr int kXfLineWords = 16;           // 64-bit words per 128-byte line
+constexpr int kXfHalfWords = 8;
+constexpr int kXfTicketStride = 32;        // in uint32: one counter per line
+constexpr int kXfXccs = 16;                // XCC_ID[3:0]
+constexpr int kXfMaxRecords = 4096;
+constexpr int kXfMaxBlocks = 1024;
+constexpr int kXfStaggerSleeps = 2;        // x s_sleep(127), 64 clocks each unit
+constexpr uint64_t kXfStaticKey = 0x5354415449435F58ull;
+constexpr uint64_t kXfAtomKey1 = 0x41544F4D31ull, kXfAtomKey2 = 0x41544F4D32ull,
+                   kXfAtomKey3 = 0x41544F4D33ull;
+constexpr int64_t kXfF32Bound = 1ll << 23;
+constexpr unsigned kXfPoisonPayload = 1u << 0, kXfPoisonHeader = 1u << 1,
+                   kXfPoisonAdd32 = 1u << 2, kXfPoisonAdd64 = 1u << 3,
+                   kXfPoisonAddF32 = 1u << 4, kXfPoisonMinMax = 1u << 5,
+                   kXfPoisonBitwise = 1u << 6, kXfPoisonTickets = 1u << 7,
+                   kXfPoisonCas = 1u << 8;
+constexpr int kXfPoisonBits = 9;
+constexpr uint32_t kXfKindPayload = 0, kXfKindHeader = 1;
+
+// Device-side counters of the hand-off sweep.
+constexpr int kXfCtlPayloadErrors = 0, kXfCtlHeaderErrors = 1, kXfCtlClaims = 2,
+              kXfCtlEpisodes = 3, kXfCtlHeaderWords = 4, kXfCtlTicketRange = 5,
+              kXfCtlWriterRange = 6, kXfCtlWords = 8;
+// LDS of the hand-off kernel, one object: the ticket and neighbour-mask
+// broadcast, the header words, then per writer XCC the payload words compared
+// in the episode's own group, mismatching, and compared in neighbour groups.
+constexpr int kXfShTicket = 0, kXfShMask = 1, kXfShHeader = 2, kXfShWords = 3,
+              kXfShErrors = 3 + kXfXccs, kXfShExtra = 3 + 2 * kXfXccs,
+              kXfShSize = 3 + 3 * kXfXccs;
+constexpr int kXfPairWords = 0, kXfPairErrors = 1, kXfPairExtra = 2,
+              kXfPairPlanes = 3;
+constexpr uint32_t kXfExtraGroups = 2;     // neighbour groups a reducer may add
+
+struct XfRecord {
+  uint32_t round, rep, group, member, line, word, writer_xcc, reader_xcc, kind,
+      extra;
+  uint64_t expected, got;
+};
+
+struct XfHandoff {
+  uint64_t* slab;
+  uint32_t* tickets;       // [reps][G], kXfTicketStride apart
+  uint32_t* writer_xcc;    // [reps][blocks]
+  unsigned long long* ctl;
+  unsigned long long* pair;  // [3][16][16]: words | mismatching | extra words
+  XfRecord* records;
+  uint64_t seed;
+  uint32_t round, reps, group, G, slab_lines, max_records, poison_mask;
+  int poison_pair;
+};
+
+__host__ __device__ inline uint64_t xf_static_word(uint64_t seed, uint64_t idx) {
+  return hbm_pattern_value(kHbmPatternHash, seed ^ kXfStaticKey, idx);
+}
+// round -1 is the initial upload
+__host__ __device__ inline uint64_t xf_payload_word(uint64_t seed, int64_t round,
+                                                    uint64_t idx) {
+  return hbm_pattern_value(kHbmPatternHash, seed + (uint64_t)round, idx);
+}
+__host__ __device__ inline uint64_t xf_line_index(uint32_t blocks,
+                                                  uint32_t slab_lines,
+                                                  uint32_t rep, uint32_t block,
+                                                  uint32_t line) {
+  return ((uint64_t)rep * blocks + block) * slab_lines + line;
+}
+
+// the rare path: claim a record slot, as hbm_report does
+__device__ __forceinline__ void xf_report(const XfHandoff& a, uint32_t rep,
+                                          uint32_t group, uint32_t member,
+                                          uint32_t line, uint32_t word,
+                                          uint32_t wx, uint32_t rx, uint32_t kind,
+                                          uint32_t extra, uint64_t expected,
+                                          uint64_t got) {
+  const unsigned long long slot = atomicAdd(&a.ctl[kXfCtlClaims], 1ull);
+  if (slot < a.max_records) {  // claims past the cap are dropped
+    XfRecord r = {a.round, rep, group, member, line, word, wx, rx, kind, extra,
+                  expected, got};
+    a.records[slot] = r;
+  }
+}
+
+// All waves of a reducer compare every payload half of group `vg` at
+// repetition `vrep` with plain 16-byte loads; `plane` is where the compared
+// words are counted (the episode's own group, or a neighbour group).
+__device__ __forceinline__ void xf_verify_group(const XfHandoff& a, uint32_t* sh,
+                                                int plane, uint32_t extra,
+                                                uint32_t vrep, uint32_t vg,
+                                                uint32_t rx,
+                                                uint32_t& writer_range) {
+  const uint32_t blocks = a.group * a.G;
+  const uint32_t slab_vecs = a.slab_lines * 4;
+  const uint32_t group_vecs = a.group * slab_vecs;
+  for (uint32_t v = threadIdx.x; v < group_vecs; v += kXfBlock) {
+    const uint32_t m = v / slab_vecs, rem = v % slab_vecs;
+    const uint32_t line = rem >> 2, w = kXfHalfWords + (rem & 3) * 2;
+    const uint32_t blk = vg + m * a.G;
+    const uint32_t wx = a.writer_xcc[(size_t)vrep * blocks + blk];
+    const uint64_t idx =
+        xf_line_index(blocks, a.slab_lines, vrep, blk, line) * kXfLineWords + w;
+    const u64x2 got = *reinterpret_cast<const u64x2*>(a.slab + idx);
+    if (wx >= (uint32_t)kXfXccs) {  // guarded before it indexes anything
+      if ((rem & 3) == 0 && line == 0) ++writer_range;
+      continue;
+    }
+    // test hook: data only, flips bit 0 of the *expected* words
+    const uint64_t px =
+        ((a.poison_mask & kXfPoisonPayload) &&
+         (a.poison_pair < 0 || (uint32_t)a.poison_pair == ((wx << 4) | rx)))
+            ? 1ull : 0ull;
+    uint32_t bad = 0;
+    for (int k = 0; k < 2; ++k) {
+      const uint64_t want = xf_payload_word(a.seed, a.round, idx + k) ^ px;
+      if (got[k] != want) {
+        ++bad;
+        xf_report(a, vrep, vg, m, line, w + k, wx, rx, kXfKindPayload, extra,
+                  want, got[k]);
+      }
+    }
+    atomicAdd(&sh[plane + wx], 2u);
+    if (bad) atomicAdd(&sh[kXfShErrors + wx], bad);
+  }
+}
+
+// The j-th neighbour group of episode (round, rep, g): never g itself, and a
+// different one every repetition and round.  Needs G > 1.
+__device__ __forceinline__ uint32_t xf_neighbour(const XfHandoff& a, uint32_t rep,
+                                                 uint32_t g, uint32_t j) {
+  return (g + 1 + (j + kXfExtraGroups * (rep + a.round)) % (a.G - 1)) % a.G;
+}
+
+// A fixed idle time of a few microseconds, the same for every caller.
+__device__ __forceinline__ void xf_stagger() {
+  for (int i = 0; i < kXfStaggerSleeps; ++i) __builtin_amdgcn_s_sleep(127);
+}
+
+__global__ void __launch_bounds__(kXfBlock) xcd_handoff_kernel(XfHandoff a) {
+#if defined(__gfx950__)
+  __shared__ uint32_t sh[kXfShSize];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t rx = __builtin_amdgcn_s_getreg(kCovHwRegXccId) & (kXfXccs - 1);
+  const uint32_t blocks = a.group * a.G;  // the host launches exactly this grid
+  const uint32_t b = blockIdx.x;
+  const uint32_t member = b / a.G, g = b % a.G;
+  const uint32_t slab_vecs = a.slab_lines * 4;  // 16-byte vectors per half slab
+  const uint32_t group_vecs = a.group * slab_vecs;
+  // test hook: data only, flips bit 0 of the *expected* words
+  const uint64_t px_header =
+      ((a.poison_mask & kXfPoisonHeader) &&
+       (a.poison_pair < 0 ||
+        (uint32_t)(a.poison_pair & (kXfXccs - 1)) == rx))
+          ? 1ull : 0ull;
+  uint32_t episodes = 0, ticket_range = 0, writer_range = 0, header_bad = 0,
+           header_words = 0;
+
+  if (tid < kXfShSize) sh[tid] = 0;
+  __syncthreads();
+
+  for (uint32_t rep = 0; rep < a.reps; ++rep) {
+    // 1. pre-touch: the static halves of the whole group, nobody writes them
+    for (uint32_t v = tid; v < group_vecs; v += kXfBlock) {
+      const uint32_t m = v / slab_vecs, rem = v % slab_vecs;
+      const uint32_t line = rem >> 2, w = (rem & 3) * 2;
+      const uint64_t idx =
+          xf_line_index(blocks, a.slab_lines, rep, g + m * a.G, line) *
+              kXfLineWords + w;
+      const u64x2 got = *reinterpret_cast<const u64x2*>(a.slab + idx);
+      header_words += 2;
+      for (int k = 0; k < 2; ++k) {
+        const uint64_t want = xf_static_word(a.seed, idx + k) ^ px_header;
+        if (got[k] != want) {
+          ++header_bad;
+          // a static word has no device writer: writer_xcc is 0xFFFFFFFF
+          xf_report(a, rep, g, m, line, w + k, 0xFFFFFFFFu, rx, kXfKindHeader,
+                    0u, want, got[k]);
+        }
+      }
+    }
+
+    // 2. write the payload halves of this block's own slab, and who wrote it
+    if (tid < slab_vecs) {
+      const uint32_t line = tid >> 2, w = kXfHalfWords + (tid & 3) * 2;
+      const uint64_t idx =
+          xf_line_index(blocks, a.slab_lines, rep, b, line) * kXfLineWords + w;
+      u64x2 p;
+      p[0] = xf_payload_word(a.seed, a.round, idx);
+      p[1] = xf_payload_word(a.seed, a.round, idx + 1);
+      *reinterpret_cast<u64x2*>(a.slab + idx) = p;
+    }
+    if (tid == 0) a.writer_xcc[(size_t)rep * blocks + b] = rx;
+
+    // 3. release and ticket: every wave drains its stores, one lane writes the
+    // L2 back, waits for that itself, and only then draws the ticket
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      // stagger (see above): one member per episode idles before its ticket,
+      // the others after theirs, so nobody falls behind from rep to rep
+      const bool late = member == (rep + a.round) % a.group;
+      if (late) xf_stagger();
+      const uint32_t t = __hip_atomic_fetch_add(
+          &a.tickets[((size_t)rep * a.G + g) * kXfTicketStride], 1u,
+          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (!late) xf_stagger();
+      if (t == a.group - 1) {  // 4. the last arriver acquires for the workgroup
+        // one look, no loop: a neighbour group whose previous episode already
+        // holds all its tickets has released all its slabs, so the acquire
+        // below covers them too; one that does not is simply left out
+        uint32_t mask = 0;
+        if (rep > 0 && a.G > 1) {
+          const uint32_t n = a.G - 1 < kXfExtraGroups ? a.G - 1 : kXfExtraGroups;
+          for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t g2 = xf_neighbour(a, rep, g, j);
+            if (atomicCAS(&a.tickets[((size_t)(rep - 1) * a.G + g2) *
+                                     kXfTicketStride],
+                          a.group, a.group) == a.group)
+              mask |= 1u << j;
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        sh[kXfShMask] = mask;
+      }
+      sh[kXfShTicket] = t;
+    }
+    __syncthreads();
+    const uint32_t ticket = sh[kXfShTicket];
+    if (ticket >= a.group) {  // never used for anything but this count
+      if (tid == 0) ++ticket_range;
+      continue;
+    }
+    if (ticket != a.group - 1) continue;  // everyone else goes on
+
+    xf_verify_group(a, sh, kXfShWords, 0u, rep, g, rx, writer_range);
+    const uint32_t mask = sh[kXfShMask];
+    for (uint32_t j = 0; j < kXfExtraGroups; ++j)
+      if (mask & (1u << j))
+        xf_verify_group(a, sh, kXfShExtra, 1u, rep - 1,
+                        xf_neighbour(a, rep, g, j), rx, writer_range);
+    if (tid == 0) ++episodes;
+  }
+
+  // one flush per workgroup: its reader XCC is the same for every episode
+  atomicAdd(&sh[kXfShHeader], header_words);
+  if (header_bad)
+    atomicAdd(&a.ctl[kXfCtlHeaderErrors], (unsigned long long)header_bad);
+  if (writer_range)
+    atomicAdd(&a.ctl[kXfCtlWriterRange], (unsigned long long)writer_range);
+  __syncthreads();
+  if (tid < (uint32_t)kXfXccs) {
+    const uint32_t words = sh[kXfShWords + tid], errs = sh[kXfShErrors + tid];
+    const uint32_t extra = sh[kXfShExtra + tid];
+    constexpr int kPlane = kXfXccs * kXfXccs;
+    const uint32_t at = tid * kXfXccs + rx;
+    if (words)
+      atomicAdd(&a.pair[kXfPairWords * kPlane + at], (unsigned long long)words);
+    if (extra)
+      atomicAdd(&a.pair[kXfPairExtra * kPlane + at], (unsigned long long)extra);
+    if (errs) {
+      atomicAdd(&a.pair[kXfPairErrors * kPlane + at], (unsigned long long)errs);
+      atomicAdd(&a.ctl[kXfCtlPayloadErrors], (unsigned long long)errs);
+    }
+  }
+  if (tid == 0) {
+    atomicAdd(&a.ctl[kXfCtlHeaderWords], (unsigned long long)sh[kXfShHeader]);
+    if (episodes)
+      atomicAdd(&a.ctl[kXfCtlEpisodes], (unsigned long long)episodes);
+    if (ticket_range)
+      atomicAdd(&a.ctl[kXfCtlTicketRange], (unsigned long long)ticket_range);
+  }
+#endif
+}
+
+// One target of the atomics sweep: every operand on the same 128-byte line.
+struct alignas(128) XfCell {
+  unsigned long long add64, max64, min64;
+  uint32_t add32;
+  float addf;
+  uint32_t x, o, a, claim, confirm;
+};
+static_assert(sizeof(XfCell) == 128, "one cell per 128-byte line");
+
+struct XfAtomVals {
+  uint64_t add64, mm;
+  uint32_t add32, x, o, a;
+  int addf;  // integer in [-8, 8], added as f32
+};
+
+// The one generator shared by the kernel and the host: what thread `id` adds
+// in repetition `rep`.  or/and operands are mostly neutral so the cells do
+// not saturate.
+__host__ __device__ inline XfAtomVals xf_atom_vals(uint64_t seed, uint64_t id,
+                                                   uint32_t rep) {
+  const uint64_t n = id * 64 + rep;
+  const uint64_t h1 = hbm_pattern_value(kHbmPatternHash, seed ^ kXfAtomKey1, n);
+  const uint64_t h2 = hbm_pattern_value(kHbmPatternHash, seed ^ kXfAtomKey2, n);
+  const uint64_t h3 = hbm_pattern_value(kHbmPatternHash, seed ^ kXfAtomKey3, n);
+  XfAtomVals v;
+  v.add32 = (uint32_t)h1;
+  v.addf = (int)((h1 >> 32) % 17) - 8;
+  v.add64 = h2;
+  v.mm = h3;
+  v.x = (uint32_t)(h1 >> 20);
+  v.o = ((h2 >> 40) & 1023) == 0 ? 1u << ((h2 >> 8) & 31) : 0u;
+  v.a = ((h2 >> 50) & 1023) == 0 ? ~(1u << ((h2 >> 16) & 31)) : ~0u;
+  return v;
+}
+
+constexpr int kXfActlTicketRange = 0, kXfActlWords = 2;
+
+struct XfAtomics {
+  XfCell* cells;
+  uint32_t* ticket;        // one counter on its own line
+  uint32_t* seen;          // [total]
+  uint32_t* adders;        // [16] waves per XCC
+  unsigned long long* ctl;
+  uint64_t seed;
+  uint32_t reps, ncells, total;
+};
+
+__global__ void __launch_bounds__(kXfBlock) xcd_atomics_kernel(XfAtomics a) {
+#if defined(__gfx950__)
+  const uint32_t id = blockIdx.x * kXfBlock + threadIdx.x;
+  if (id >= a.total) return;  // the host launches exactly total threads
+  for (uint32_t rep = 0; rep < a.reps; ++rep) {
+    XfCell* c = &a.cells[(id + rep) % a.ncells];
+    const XfAtomVals v = xf_atom_vals(a.seed, id, rep);
+    __hip_atomic_fetch_add(&c->add32, v.add32, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&c->add64, (unsigned long long)v.add64,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsafeAtomicAdd(&c->addf, (float)v.addf);  // the hardware f32 add
+    __hip_atomic_fetch_max(&c->max64, (unsigned long long)v.mm, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_min(&c->min64, (unsigned long long)v.mm, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_xor(&c->x, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_or(&c->o, v.o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_and(&c->a, v.a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // returning add: a ticket is an index only after its range check
+  const uint32_t t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+  if (t < a.total)
+    a.seen[t] = id + 1;
+  else
+    atomicAdd(&a.ctl[kXfActlTicketRange], 1ull);
+  // single-shot CAS: one attempt, the winner confirms
+  XfCell* k = &a.cells[id % a.ncells];
+  if (atomicCAS(&k->claim, 0u, id + 1) == 0u) k->confirm = id + 1;
+  if ((threadIdx.x & 63) == 0)
+    atomicAdd(&a.adders[__builtin_amdgcn_s_getreg(kCovHwRegXccId) & (kXfXccs - 1)],
+              1u);
+#endif
+}
+
+// Expected cell contents after `threads` threads ran `reps` repetitions.
+struct XfAtomExpected {
+  std::vector<uint32_t> add32, x, o, a;
+  std::vector<uint64_t> add64, max64, min64;
+  std::vector<int64_t> addf;
+};
+
+static XfAtomExpected xf_atom_expected(uint64_t seed, uint64_t threads, int reps,
+                                       int cells) {
+  XfAtomExpected e;
+  e.add32.assign(cells, 0u);
+  e.x.assign(cells, 0u);
+  e.o.assign(cells, 0u);
+  e.a.assign(cells, ~0u);
+  e.add64.assign(cells, 0ull);
+  e.max64.assign(cells, 0ull);
+  e.min64.assign(cells, ~0ull);
+  e.addf.assign(cells, 0);
+  std::vector<int64_t> mag(cells, 0);
+  for (uint64_t id = 0; id < threads; ++id)
+    for (int rep = 0; rep < reps; ++rep) {
+      const size_t c = (size_t)((id + (uint64_t)rep) % (uint64_t)cells);
+      const XfAtomVals v = xf_atom_vals(seed, id, (uint32_t)rep);
+      e.add32[c] += v.add32;
+      e.add64[c] += v.add64;
+      e.addf[c] += v.addf;
+      mag[c] += v.addf < 0 ? -v.addf : v.addf;
+      e.max64[c] = std::max(e.max64[c], v.mm);
+      e.min64[c] = std::min(e.min64[c], v.mm);
+      e.x[c] ^= v.x;
+      e.o[c] |= v.o;
+      e.a[c] &= v.a;
+    }
+  // enforced, not assumed: below 2^23 every partial sum is an exact f32
+  for (int c = 0; c < cells; ++c)
+    if (mag[c] > kXfF32Bound)
+      throw std::invalid_argument(
+          "xcd_fabric: the f32 operands of cell " + std::to_string(c) +
+          " sum to a magnitude of " + std::to_string(mag[c]) +
+          " > 2^23; use more cells or fewer reps");
+  return e;
+}
+
+struct XfShape {
+  int reps, group, slab_lines, cells, blocks, max_rounds, max_records;
+  unsigned poison_mask;
+  int poison_pair;
+};
+
+// every argument is validated here, before the first HIP call
+static void xf_validate(const std::string& who, const XfShape& s) {
+  if (s.reps < 1 || s.reps > 64)
+    throw std::invalid_argument(who + ": reps must be in [1, 64]");
+  if (s.group < 2 || s.group > 64)
+    throw std::invalid_argument(who + ": group must be in [2, 64]");
+  if (s.slab_lines < 1 || s.slab_lines > 32)
+    throw std::invalid_argument(who + ": slab_lines must be in [1, 32]");
+  if (s.cells < 1 || s.cells > 4096)
+    throw std::invalid_argument(who + ": cells must be in [1, 4096]");
+  if (s.blocks < 0 || s.blocks > kXfMaxBlocks ||
+      (s.blocks > 0 && s.blocks % s.group != 0))
+    throw std::invalid_argument(
+        who + ": blocks must be 0 (derive from the device) or a positive "
+              "multiple of group, at most 1024");
+  if (s.max_rounds < 2 || s.max_rounds > 64)
+    throw std::invalid_argument(who + ": max_rounds must be in [2, 64]");
+  if (s.max_records < 1 || s.max_records > kXfMaxRecords)
+    throw std::invalid_argument(who + ": max_records must be in [1, 4096]");
+  if (s.poison_mask >= (1u << kXfPoisonBits))
+    throw std::invalid_argument(who + ": poison_mask has 9 bits");
+  if (s.poison_pair < -1 || s.poison_pair > 0xFF)
+    throw std::invalid_argument(
+        who + ": poison_pair is -1 or writer_xcc << 4 | reader_xcc");
+}
+
+static py::dict xf_expected_dict(const XfAtomExpected& e) {
+  py::dict d;
+  d["add_u32"] = e.add32;
+  d["add_u64"] = e.add64;
+  std::vector<double> f(e.addf.begin(), e.addf.end());
+  d["add_f32"] = f;
+  d["max_u64"] = e.max64;
+  d["min_u64"] = e.min64;
+  d["xor_u32"] = e.x;
+  d["or_u32"] = e.o;
+  d["and_u32"] = e.a;
+  return d;
+}
+
+// host only: no HIP call
+static py::dict xcd_fabric_reference(int blocks, uint64_t seed, int reps,
+                                     int group, int slab_lines, int cells,
+                                     int round, int rep, int block, int line,
+                                     uint64_t threads) {
+  const XfShape s = {reps, group, slab_lines, cells, blocks, 2, 1, 0u, -1};
+  xf_validate("xcd_fabric_reference", s);
+  if (blocks < 1)
+    throw std::invalid_argument("xcd_fabric_reference: blocks must be given");
+  if (round < -1 || round >= 64)
+    throw std::invalid_argument("xcd_fabric_reference: round must be in [-1, 63]");
+  if (rep < 0 || rep >= reps || block < 0 || block >= blocks || line < 0 ||
+      line >= slab_lines)
+    throw std::invalid_argument(
+        "xcd_fabric_reference: rep, block or line out of the shape");
+  if (threads > (1ull << 22))
+    throw std::invalid_argument("xcd_fabric_reference: threads is at most 2^22");
+  const uint64_t first =
+      xf_line_index((uint32_t)blocks, (uint32_t)slab_lines, (uint32_t)rep,
+                    (uint32_t)block, (uint32_t)line) * kXfLineWords;
+  std::vector<uint64_t> header(kXfHalfWords), payload(kXfHalfWords);
+  for (int w = 0; w < kXfHalfWords; ++w) {
+    header[w] = xf_static_word(seed, first + w);
+    payload[w] = xf_payload_word(seed, round, first + kXfHalfWords + w);
+  }
+  py::dict out;
+  out["first_word"] = first;
+  out["header"] = header;
+  out["payload"] = payload;
+  out["member"] = block / (blocks / group);
+  out["group_index"] = block % (blocks / group);
+  if (threads > 0)
+    out["atomics"] = xf_expected_dict(xf_atom_expected(seed, threads, reps, cells));
+  else
+    out["atomics"] = py::none();
+  return out;
+}
+
+static uint32_t xf_f32_bits(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, sizeof(u));
+  return u;
+}
+
+static void xf_mismatch(py::list& out, const char* comparison, const char* op,
+                        int cell, py::object expected, py::object got) {
+  py::dict e;
+  e["comparison"] = comparison;
+  e["op"] = op;
+  e["cell"] = cell;
+  e["expected"] = expected;
+  e["got"] = got;
+  out.append(e);
+}
+
+static py::dict xf_run_atomics(int cus, const XfShape& s, uint64_t seed,
+                               double& elapsed_ms) {
+  const uint32_t grid = 2u * (uint32_t)cus;
+  const uint32_t total = grid * kXfBlock;
+  // throws when the f32 bound does not hold for this device's thread count
+  const XfAtomExpected e = xf_atom_expected(seed, total, s.reps, s.cells);
+
+  std::vector<XfCell> cells((size_t)s.cells);
+  std::memset(cells.data(), 0, sizeof(XfCell) * cells.size());
+  for (XfCell& c : cells) {
+    c.min64 = ~0ull;
+    c.a = ~0u;
+  }
+  HbmDeviceBuf d_cells, d_ticket, d_seen, d_adders, d_ctl;
+  d_cells.alloc(sizeof(XfCell) * cells.size());
+  d_ticket.alloc(128);
+  d_seen.alloc(sizeof(uint32_t) * total);
+  d_adders.alloc(sizeof(uint32_t) * kXfXccs);
+  d_ctl.alloc(sizeof(uint64_t) * kXfActlWords);
+  HIP_CHECK(hipMemcpy(d_cells.ptr, cells.data(), sizeof(XfCell) * cells.size(),
+                      hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_ticket.ptr, 0, 128));
+  HIP_CHECK(hipMemset(d_seen.ptr, 0, sizeof(uint32_t) * total));
+  HIP_CHECK(hipMemset(d_adders.ptr, 0, sizeof(uint32_t) * kXfXccs));
+  HIP_CHECK(hipMemset(d_ctl.ptr, 0, sizeof(uint64_t) * kXfActlWords));
+  CovEvent t0, t1;
+  t0.create();
+  t1.create();
+
+  XfAtomics a;
+  a.cells = static_cast<XfCell*>(d_cells.ptr);
+  a.ticket = static_cast<uint32_t*>(d_ticket.ptr);
+  a.seen = static_cast<uint32_t*>(d_seen.ptr);
+  a.adders = static_cast<uint32_t*>(d_adders.ptr);
+  a.ctl = static_cast<unsigned long long*>(d_ctl.ptr);
+  a.seed = seed;
+  a.reps = (uint32_t)s.reps;
+  a.ncells = (uint32_t)s.cells;
+  a.total = total;
+  HIP_CHECK(hipEventRecord(t0.ev));
+  hipLaunchKernelGGL(xcd_atomics_kernel, dim3(grid), dim3(kXfBlock), 0, 0, a);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(t1.ev));
+  HIP_CHECK(hipEventSynchronize(t1.ev));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+  elapsed_ms += ms;
+
+  std::vector<uint32_t> seen(total), adders(kXfXccs);
+  uint32_t counter = 0;
+  uint64_t ctl[kXfActlWords];
+  HIP_CHECK(hipMemcpy(cells.data(), d_cells.ptr, sizeof(XfCell) * cells.size(),
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(seen.data(), d_seen.ptr, sizeof(uint32_t) * total,
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(adders.data(), d_adders.ptr, sizeof(uint32_t) * kXfXccs,
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(&counter, d_ticket.ptr, sizeof(counter),
+                      hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(ctl, d_ctl.ptr, sizeof(ctl), hipMemcpyDeviceToHost));
+
+  // test hook: data only, bit 0 of the expected value
+  const auto px = [&](unsigned bit) { return (s.poison_mask & bit) ? 1u : 0u; };
+  py::list mism;
+  XfAtomExpected g = e;  // same shape, filled with what the device holds
+  std::vector<double> got_f((size_t)s.cells);
+  std::vector<uint32_t> claims((size_t)s.cells), confirms((size_t)s.cells);
+  for (int c = 0; c < s.cells; ++c) {
+    const XfCell& k = cells[(size_t)c];
+    g.add32[c] = k.add32;
+    g.add64[c] = k.add64;
+    g.max64[c] = k.max64;
+    g.min64[c] = k.min64;
+    g.x[c] = k.x;
+    g.o[c] = k.o;
+    g.a[c] = k.a;
+    got_f[c] = (double)k.addf;
+    claims[c] = k.claim;
+    confirms[c] = k.confirm;
+    const uint32_t w32 = e.add32[c] ^ px(kXfPoisonAdd32);
+    if (k.add32 != w32)
+      xf_mismatch(mism, "add_u32", "add_u32", c, py::int_(w32), py::int_(k.add32));
+    const uint64_t w64 = e.add64[c] ^ (uint64_t)px(kXfPoisonAdd64);
+    if (k.add64 != w64)
+      xf_mismatch(mism, "add_u64", "add_u64", c, py::int_(w64), py::int_(k.add64));
+    const uint32_t wf = xf_f32_bits((float)e.addf[c]) ^ px(kXfPoisonAddF32);
+    if (xf_f32_bits(k.addf) != wf) {
+      float want;
+      std::memcpy(&want, &wf, sizeof(want));
+      xf_mismatch(mism, "add_f32", "add_f32", c, py::float_((double)want),
+                  py::float_((double)k.addf));
+    }
+    const uint64_t wmax = e.max64[c] ^ (uint64_t)px(kXfPoisonMinMax);
+    const uint64_t wmin = e.min64[c] ^ (uint64_t)px(kXfPoisonMinMax);
+    if (k.max64 != wmax)
+      xf_mismatch(mism, "minmax", "max_u64", c, py::int_(wmax), py::int_(k.max64));
+    if (k.min64 != wmin)
+      xf_mismatch(mism, "minmax", "min_u64", c, py::int_(wmin), py::int_(k.min64));
+    const uint32_t pb = px(kXfPoisonBitwise);
+    if (k.x != (e.x[c] ^ pb))
+      xf_mismatch(mism, "bitwise", "xor_u32", c, py::int_(e.x[c] ^ pb), py::int_(k.x));
+    if (k.o != (e.o[c] ^ pb))
+      xf_mismatch(mism, "bitwise", "or_u32", c, py::int_(e.o[c] ^ pb), py::int_(k.o));
+    if (k.a != (e.a[c] ^ pb))
+      xf_mismatch(mism, "bitwise", "and_u32", c, py::int_(e.a[c] ^ pb), py::int_(k.a));
+    // the winner of slot c is some thread id with id % cells == c
+    const bool contested = (uint32_t)c < total;
+    const uint32_t want_confirm = k.claim ^ px(kXfPoisonCas);
+    const bool claim_ok =
+        contested ? (k.claim != 0 && k.claim <= total &&
+                     (k.claim - 1) % (uint32_t)s.cells == (uint32_t)c)
+                  : k.claim == 0;
+    if (!claim_ok || k.confirm != want_confirm)
+      xf_mismatch(mism, "cas", "cas", c, py::int_(want_confirm),
+                  py::int_(k.confirm));
+  }
+  // every ticket drawn exactly once: counter == total and no hole in seen
+  uint64_t missing = 0, seen_range = 0;
+  for (uint32_t t = 0; t < total; ++t) {
+    missing += seen[t] == 0;
+    seen_range += seen[t] > total;
+  }
+  const uint32_t want_total = total ^ px(kXfPoisonTickets);
+  if (counter != want_total)
+    xf_mismatch(mism, "tickets", "tickets", -1, py::int_(want_total),
+                py::int_(counter));
+
+  py::dict got = xf_expected_dict(g);
+  got["add_f32"] = got_f;
+  py::dict out;
+  out["workgroups"] = grid;
+  out["threads"] = total;
+  out["totals"] = got;
+  out["expected"] = xf_expected_dict(e);
+  out["mismatches"] = mism;
+  out["ticket_counter"] = counter;
+  out["tickets_expected"] = total;
+  out["tickets_missing"] = missing;
+  out["tickets_out_of_range"] = ctl[kXfActlTicketRange] + seen_range;
+  out["claims"] = claims;
+  out["confirms"] = confirms;
+  out["adders_per_xcc"] = adders;
+  out["ms"] = (double)ms;
+  return out;
+}
+
+static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines,
+                                 int cells, int blocks, int max_rounds,
+                                 uint64_t seed, int max_records,
+                                 unsigned poison_mask, int poison_pair) {
+  const XfShape s = {reps, group, slab_lines, cells, blocks, max_rounds,
+                     max_records, poison_mask, poison_pair};
+  xf_validate("xcd_fabric_check", s);
+
+  hipDeviceProp_t prop;
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipGetDeviceProperties(&prop, device));
+  const int cus = prop.multiProcessorCount;
+  if (cus < 1 || cus > kCovKeys)
+    throw std::runtime_error("xcd_fabric_check: implausible compute unit count");
+  // G: the largest odd number with group x G <= 2 x CUs (at least one group)
+  int G = blocks > 0 ? blocks / group : (2 * cus) / group;
+  if (blocks == 0) {
+    if (G < 1) G = 1;
+    if ((G & 1) == 0) --G;
+  }
+  const uint32_t nblocks = (uint32_t)(group * G);
+  const size_t lines = (size_t)reps * nblocks * (size_t)slab_lines;
+  const size_t slab_words = lines * kXfLineWords;
+  const size_t n_tickets = (size_t)reps * (size_t)G;
+  const size_t ticket_bytes = n_tickets * kXfTicketStride * sizeof(uint32_t);
+  const size_t writer_count = (size_t)reps * nblocks;
+  constexpr size_t kPlane = (size_t)kXfXccs * kXfXccs;
+  const size_t pair_bytes = sizeof(uint64_t) * kXfPairPlanes * kPlane;
+
+  // the initial upload plays round -1
+  std::vector<uint64_t> h_slab(slab_words);
+  for (size_t i = 0; i < slab_words; ++i)
+    h_slab[i] = (i % kXfLineWords) < (size_t)kXfHalfWords
+                    ? xf_static_word(seed, i)
+                    : xf_payload_word(seed, -1, i);
+
+  HbmDeviceBuf d_slab, d_tickets, d_writer, d_ctl, d_pair, d_records;
+  d_slab.alloc(slab_words * sizeof(uint64_t));
+  d_tickets.alloc(ticket_bytes);
+  d_writer.alloc(writer_count * sizeof(uint32_t));
+  d_ctl.alloc(sizeof(uint64_t) * kXfCtlWords);
+  d_pair.alloc(pair_bytes);
+  d_records.alloc(sizeof(XfRecord) * (size_t)max_records);
+  HIP_CHECK(hipMemcpy(d_slab.ptr, h_slab.data(), slab_words * sizeof(uint64_t),
+                      hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemset(d_writer.ptr, 0xFF, writer_count * sizeof(uint32_t)));
+  HIP_CHECK(hipMemset(d_ctl.ptr, 0, sizeof(uint64_t) * kXfCtlWords));
+  HIP_CHECK(hipMemset(d_pair.ptr, 0, pair_bytes));
+  HIP_CHECK(hipMemset(d_records.ptr, 0, sizeof(XfRecord) * (size_t)max_records));
+  CovEvent t0, t1;
+  t0.create();
+  t1.create();
+
+  std::vector<uint32_t> h_tickets(n_tickets * kXfTicketStride);
+  std::vector<uint32_t> h_writer(writer_count);
+  std::vector<uint64_t> h_pair(kXfPairPlanes * kPlane);
+  std::vector<uint64_t> writes_per_xcc(kXfXccs, 0);
+  uint64_t ticket_counter_errors = 0, writer_host_range = 0;
+  int rounds = 0, pairs_covered = 0, xcc_seen = 0;
+  unsigned xcc_mask = 0;
+  double elapsed_ms = 0.0;
+  py::list round_ms;
+  while (rounds < max_rounds) {
+    XfHandoff a;
+    a.slab = static_cast<uint64_t*>(d_slab.ptr);
+    a.tickets = static_cast<uint32_t*>(d_tickets.ptr);
+    a.writer_xcc = static_cast<uint32_t*>(d_writer.ptr);
+    a.ctl = static_cast<unsigned long long*>(d_ctl.ptr);
+    a.pair = static_cast<unsigned long long*>(d_pair.ptr);
+    a.records = static_cast<XfRecord*>(d_records.ptr);
+    a.seed = seed;
+    a.round = (uint32_t)rounds;
+    a.reps = (uint32_t)reps;
+    a.group = (uint32_t)group;
+    a.G = (uint32_t)G;
+    a.slab_lines = (uint32_t)slab_lines;
+    a.max_records = (uint32_t)max_records;
+    a.poison_mask = poison_mask;
+    a.poison_pair = poison_pair;
+    HIP_CHECK(hipEventRecord(t0.ev));
+    // the ticket counters are zeroed on the launch stream ahead of every launch
+    HIP_CHECK(hipMemsetAsync(d_tickets.ptr, 0, ticket_bytes, 0));
+    hipLaunchKernelGGL(xcd_handoff_kernel, dim3(nblocks), dim3(kXfBlock), 0, 0, a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(t1.ev));
+    HIP_CHECK(hipEventSynchronize(t1.ev));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+    elapsed_ms += ms;
+    round_ms.append((double)ms);
+    ++rounds;
+
+    HIP_CHECK(hipMemcpy(h_tickets.data(), d_tickets.ptr, ticket_bytes,
+                        hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_writer.data(), d_writer.ptr,
+                        writer_count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_pair.data(), d_pair.ptr, pair_bytes,
+                        hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < n_tickets; ++t)
+      ticket_counter_errors += h_tickets[t * kXfTicketStride] != (uint32_t)group;
+    for (uint32_t wx : h_writer) {
+      if (wx < (uint32_t)kXfXccs) {
+        ++writes_per_xcc[wx];
+        xcc_mask |= 1u << wx;
+      } else {
+        ++writer_host_range;
+      }
+    }
+    pairs_covered = 0;
+    for (int w = 0; w < kXfXccs; ++w)
+      for (int r = 0; r < kXfXccs; ++r)
+        if (h_pair[kXfPairWords * kPlane + (size_t)w * kXfXccs + r] != 0 ||
+            h_pair[kXfPairExtra * kPlane + (size_t)w * kXfXccs + r] != 0) {
+          ++pairs_covered;
+          xcc_mask |= (1u << w) | (1u << r);
+        }
+    xcc_seen = __builtin_popcount(xcc_mask);
+    if (rounds >= 2 && pairs_covered >= xcc_seen * xcc_seen) break;
+  }
+
+  uint64_t ctl[kXfCtlWords];
+  HIP_CHECK(hipMemcpy(ctl, d_ctl.ptr, sizeof(ctl), hipMemcpyDeviceToHost));
+  const uint64_t claims = ctl[kXfCtlClaims];
+  const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)max_records);
+  std::vector<XfRecord> recs(kept);
+  if (kept)
+    HIP_CHECK(hipMemcpy(recs.data(), d_records.ptr, sizeof(XfRecord) * kept,
+                        hipMemcpyDeviceToHost));
+
+  py::dict atomics = xf_run_atomics(cus, s, seed, elapsed_ms);
+
+  py::list records;
+  for (const XfRecord& r : recs) {
+    py::dict e;
+    const bool payload = r.kind == kXfKindPayload;
+    const uint64_t idx =
+        xf_line_index(nblocks, (uint32_t)slab_lines, r.rep,
+                      r.group + r.member * (uint32_t)G, r.line) * kXfLineWords +
+        r.word;
+    e["round"] = r.round;
+    e["rep"] = r.rep;
+    e["group"] = r.group;
+    e["member"] = r.member;
+    e["block"] = r.group + r.member * (uint32_t)G;
+    e["line"] = r.line;
+    e["word"] = r.word;
+    e["writer_xcc"] = payload ? py::object(py::int_(r.writer_xcc)) : py::none();
+    e["reader_xcc"] = r.reader_xcc;
+    e["kind"] = payload ? "payload" : "header";
+    e["extra"] = r.extra != 0;
+    e["expected"] = r.expected;
+    e["got"] = r.got;
+    // what a hand-off that never happened would have read
+    e["stale"] = payload &&
+                 r.got == xf_payload_word(seed, (int64_t)r.round - 1, idx);
+    records.append(e);
+  }
+  py::list pairs;
+  uint64_t words_verified = 0, extra_words = 0;
+  for (int w = 0; w < kXfXccs; ++w)
+    for (int r = 0; r < kXfXccs; ++r) {
+      const size_t at = (size_t)w * kXfXccs + r;
+      const uint64_t words = h_pair[kXfPairWords * kPlane + at];
+      const uint64_t errs = h_pair[kXfPairErrors * kPlane + at];
+      const uint64_t extra = h_pair[kXfPairExtra * kPlane + at];
+      if (words == 0 && errs == 0 && extra == 0) continue;
+      py::dict e;
+      e["writer_xcc"] = w;
+      e["reader_xcc"] = r;
+      e["words"] = words;
+      e["lines"] = words / kXfHalfWords;
+      e["extra_lines"] = extra / kXfHalfWords;
+      e["errors"] = errs;
+      pairs.append(e);
+      words_verified += words;
+      extra_words += extra;
+    }
+  py::list xcc_ids;
+  for (int x = 0; x < kXfXccs; ++x)
+    if (xcc_mask & (1u << x)) xcc_ids.append(x);
+
+  const uint64_t episodes_per_round = (uint64_t)reps * (uint64_t)G;
+  const uint64_t group_lines = (uint64_t)group * (uint64_t)slab_lines;
+  py::dict out;
+  out["compute_units"] = cus;
+  out["seed"] = seed;
+  out["reps"] = reps;
+  out["group"] = group;
+  out["groups"] = G;
+  out["blocks"] = nblocks;
+  out["slab_lines"] = slab_lines;
+  out["cells"] = cells;
+  out["rounds"] = rounds;
+  out["max_rounds"] = max_rounds;
+  out["round_ms"] = round_ms;
+  out["episodes_completed"] = ctl[kXfCtlEpisodes];
+  out["episodes_expected"] = (uint64_t)rounds * episodes_per_round;
+  out["lines_verified"] = words_verified / kXfHalfWords;
+  out["lines_expected"] = (uint64_t)rounds * episodes_per_round * group_lines;
+  out["extra_lines_verified"] = extra_words / kXfHalfWords;
+  out["header_lines_verified"] = ctl[kXfCtlHeaderWords] / kXfHalfWords;
+  out["header_lines_expected"] =
+      (uint64_t)rounds * (uint64_t)reps * nblocks * group_lines;
+  out["payload_errors"] = ctl[kXfCtlPayloadErrors];
+  out["header_errors"] = ctl[kXfCtlHeaderErrors];
+  out["error_count"] = ctl[kXfCtlPayloadErrors] + ctl[kXfCtlHeaderErrors];
+  out["ticket_counter_errors"] = ticket_counter_errors;
+  out["tickets_out_of_range"] = ctl[kXfCtlTicketRange];
+  out["writer_xcc_out_of_range"] = ctl[kXfCtlWriterRange] + writer_host_range;
+  out["pairs"] = pairs;
+  out["pairs_covered"] = pairs_covered;
+  out["xcc_seen"] = xcc_seen;
+  out["xcc_ids"] = xcc_ids;
+  out["writes_per_xcc"] = writes_per_xcc;
+  out["records"] = records;
+  out["records_dropped"] = claims - (uint64_t)kept;
+  out["atomics"] = atomics;
+  out["elapsed_ms"] = elapsed_ms;
+  return out;
+}
+
 PYBIND11_MODULE(_gpu_validator, m) {
   m.doc() = "MI355X (gfx950) native GPU health validator";
+  m.def("xcd_fabric_check", &xcd_fabric_check, py::arg("device") = 0,
+        py::arg("reps") = 8, py::arg("group") = 16, py::arg("slab_lines") = 8,
+        py::arg("cells") = 64, py::arg("blocks") = 0, py::arg("max_rounds") = 8,
+        py::arg("seed") = 1ull, py::arg("max_records") = 64,
+        py::arg("poison_mask") = 0u, py::arg("poison_pair") = -1,
+        "Cross-XCD check: a wait-free last-arriver hand-off sweep (agent-scope "
+        "release, ticket, acquire) and a device-scope atomics sweep, exact, "
+        "coverage counted, failures attributed per (writer, reader) XCC pair");
+  m.def("xcd_fabric_reference", &xcd_fabric_reference, py::arg("blocks"),
+        py::arg("seed") = 1ull, py::arg("reps") = 8, py::arg("group") = 16,
+        py::arg("slab_lines") = 8, py::arg("cells") = 64, py::arg("round") = 0,
+        py::arg("rep") = 0, py::arg("block") = 0, py::arg("line") = 0,
+        py::arg("threads") = 0ull,
+        "Host-only: the header and payload words of one line of the hand-off "
+        "slabs and, for a thread count, the expected atomic totals");
   m.def("hbm_pattern_check", &hbm_pattern_check, py::arg("device") = 0,
         py::arg("nbytes") = 1ull << 30, py::arg("chunk_bytes") = 1ull << 30,
         py::arg("passes") = 1, py::arg("seed") = 1ull, py::arg("checker") = true,

@@ -23,7 +23,12 @@ Layers:
   matrix path (``v_mfma_scale_f32_*_f8f6f4``: e4m3, e5m2, e2m3, e3m2 and e2m1
   operands with E8M0 block scales, both shapes, mixed pairs), bit-exact, with
   failures attributed per unit (:func:`summarize_mx_matrix` is the pure
-  verdict).
+  verdict);
+- :func:`xcd_fabric_check` — opt-in cross-XCD check: wait-free last-arriver
+  hand-offs (agent-scope release, ticket, acquire) between workgroups on
+  different XCDs and a device-scope atomics sweep, exact, coverage counted,
+  failures attributed per (writer, reader) XCC pair
+  (:func:`summarize_xcd_fabric` is the pure verdict).
 """
 
 from .gpu_health import (  # noqa: F401
@@ -43,4 +48,8 @@ from .hbm_integrity import (  # noqa: F401
 from .mx_matrix import (  # noqa: F401
     mx_matrix_check,
     summarize_mx_matrix,
+)
+from .xcd_fabric import (  # noqa: F401
+    summarize_xcd_fabric,
+    xcd_fabric_check,
 )

@@ -91,6 +91,7 @@ def gpu_health_check(
     memory: bool = False,
     memory_mib: float = 4096.0,
     mx: bool = False,
+    fabric: bool = False,
 ) -> Dict[str, Any]:
     """Full node GPU health check.  Returns a report dict with a top-level
     ``healthy`` verdict; raises GpuHealthError when ``require_gpu`` and no
@@ -100,7 +101,9 @@ def gpu_health_check(
     (``0``: all free memory; see :mod:`.hbm_integrity`) and gates on it too.
     ``mx`` adds the whole-device sweep of the MX block-scaled matrix path and
     its e2m1 / e4m3 burn-in (see :mod:`.mx_matrix`); the verdict is gated on
-    the sweep and on each throughput reaching ``MFMA_MIN_TFLOPS``."""
+    the sweep and on each throughput reaching ``MFMA_MIN_TFLOPS``.  ``fabric``
+    adds the cross-XCD hand-off and device-scope atomics check (see
+    :mod:`.xcd_fabric`) and gates on it."""
     report: Dict[str, Any] = {"healthy": False, "checks": {}}
     report["checks"]["smi"] = smi_probe()
 
@@ -178,6 +181,16 @@ def gpu_health_check(
             for tf in mx_summary["throughput_tflops"].values()
         )
 
+    fabric_ok = True
+    if fabric:
+        # opt-in: agent-scope release/acquire hand-offs between XCDs and
+        # device-scope atomics, summary without raw records
+        from .xcd_fabric import summarize_xcd_fabric
+
+        fab = summarize_xcd_fabric(native.xcd_fabric_check(device))
+        report["checks"]["xcd_fabric"] = fab
+        fabric_ok = fab["healthy"]
+
     # multi-GPU nodes: verify every xGMI peer link is up
     xgmi_ok = True
     if probe.get("device_count", 1) > 1:
@@ -197,6 +210,7 @@ def gpu_health_check(
         and coverage_ok
         and memory_ok
         and mx_ok
+        and fabric_ok
     )
     return report
 
@@ -206,7 +220,8 @@ def main() -> int:
     the fp8 + burn-in checks, ``--coverage`` for the per-CU sweep and
     ``--memory`` for the HBM pattern test (``--memory-mib=N`` sets its size
     and implies it; ``N=0`` means all free memory) and ``--mx`` for the MX
-    block-scaled matrix sweep and burn-in."""
+    block-scaled matrix sweep and burn-in, ``--fabric`` for the cross-XCD
+    hand-off and atomics check."""
     import sys
 
     memory_kw: Dict[str, Any] = {}
@@ -221,6 +236,7 @@ def main() -> int:
         deep="--deep" in sys.argv,
         coverage="--coverage" in sys.argv,
         mx="--mx" in sys.argv,
+        fabric="--fabric" in sys.argv,
         **memory_kw,
     )
     print(json.dumps(report, indent=2, default=str))  # noqa: T201 (CLI/build output)
