@@ -13,6 +13,11 @@ import sysconfig
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SOURCE = os.path.join(PKG_DIR, "gpu_validator.hip")
+SOURCES = (
+    SOURCE,
+    os.path.join(PKG_DIR, "hip_util.hpp"),
+    os.path.join(PKG_DIR, "validator_problems.hpp"),
+)
 OUTPUT = os.path.join(PKG_DIR, "_gpu_validator.so")
 JSONOPS_SOURCE = os.path.join(PKG_DIR, "jsonops.cpp")
 JSONOPS_OUTPUT = os.path.join(PKG_DIR, "_jsonops.so")
@@ -28,7 +33,9 @@ CXX = os.environ.get("CXX", "g++")
 
 
 def is_built() -> bool:
-    return os.path.exists(OUTPUT) and os.path.getmtime(OUTPUT) >= os.path.getmtime(SOURCE)
+    """Stale when gpu_validator.hip or one of its headers is newer than the .so."""
+    return os.path.exists(OUTPUT) and all(
+        os.path.getmtime(OUTPUT) >= os.path.getmtime(src) for src in SOURCES)
 
 
 def build_jsonops(force: bool = False, verbose: bool = False) -> str:

@@ -32,6 +32,12 @@
 //                           device-scope atomic, exact, attributed per
 //                           (writer, reader) XCC pair (opt-in)
 //
+// This file holds the kernels, the HIP host drivers, the py::dict conversion
+// and the module table.  Device memory and events are owned by the holders in
+// hip_util.hpp (DeviceBuf<T>, EventTimer); the exact problems the checks run
+// (operands, codecs, packed tables, expected results, and the records and
+// constants shared with the kernels) are plain C++ in validator_problems.hpp.
+//
 // Built standalone with hipcc (no torch linkage) via pybind11; the .so lives
 // in-tree so it travels to GPU nodes with the package.
 
@@ -48,16 +54,10 @@
 #include <string>
 #include <vector>
 
-namespace py = pybind11;
+#include "hip_util.hpp"
+#include "validator_problems.hpp"
 
-#define HIP_CHECK(expr)                                                        \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      throw std::runtime_error(std::string("HIP error at " #expr ": ") +       \
-                               hipGetErrorString(_e));                         \
-    }                                                                          \
-  } while (0)
+namespace py = pybind11;
 
 // ---------------------------------------------------------------------------
 // MFMA f32 smoke: one wave computes D = A·B + C for a 16x16 tile, K=4,
@@ -143,119 +143,6 @@ __global__ void mfma_fp8_16x16x32_kernel(const uint8_t* __restrict__ A,
 #endif
 }
 
-static float decode_e4m3fn(uint8_t u) {
-  int s = (u >> 7) & 1;
-  int e = (u >> 3) & 0xF;
-  int m = u & 7;
-  float v;
-  if (e == 0) {
-    v = (float)m / 8.0f * (1.0f / 64.0f);  // subnormal: 2^-6 scale
-  } else if (e == 15 && m == 7) {
-    v = 0.0f;  // NaN code; never produced by our encoder
-  } else {
-    v = (1.0f + (float)m / 8.0f) * std::ldexp(1.0f, e - 7);
-  }
-  return s ? -v : v;
-}
-
-static uint8_t encode_e4m3fn_nearest(float f) {
-  // exact nearest-representable search over the 256-code table (fine for a
-  // smoke test; avoids re-deriving RNE tie rules)
-  uint8_t best = 0;
-  float best_err = 1e30f;
-  for (int u = 0; u < 256; ++u) {
-    if ((u & 0x7F) == 0x7F) continue;  // NaN codes
-    float err = std::fabs(decode_e4m3fn((uint8_t)u) - f);
-    if (err < best_err) {
-      best_err = err;
-      best = (uint8_t)u;
-    }
-  }
-  return best;
-}
-
-static py::dict mfma_bf16_tile(int device) {
-  // Run the bf16 MFMA tile and return decoded inputs + GPU output so Python
-  // tests can verify against an independent fp32 reference (e.g. torch).
-  HIP_CHECK(hipSetDevice(device));
-  const int M = 16, N = 16, K = 32;
-  std::vector<float> hAf(M * K), hBf(K * N), hD(M * N);
-  std::vector<uint16_t> hA(M * K), hB(K * N);
-  auto to_bf16 = [](float f) -> uint16_t {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    uint32_t rounded = u + 0x7FFF + ((u >> 16) & 1);
-    return (uint16_t)(rounded >> 16);
-  };
-  auto from_bf16 = [](uint16_t v) -> float {
-    uint32_t u = (uint32_t)v << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-  };
-  for (int i = 0; i < M * K; ++i) hA[i] = to_bf16(0.07f * (float)((i * 13) % 41) - 1.2f);
-  for (int i = 0; i < K * N; ++i) hB[i] = to_bf16(0.05f * (float)((i * 17) % 37) - 0.8f);
-  for (int i = 0; i < M * K; ++i) hAf[i] = from_bf16(hA[i]);
-  for (int i = 0; i < K * N; ++i) hBf[i] = from_bf16(hB[i]);
-  uint16_t *dA, *dB;
-  float* dD;
-  HIP_CHECK(hipMalloc(&dA, sizeof(uint16_t) * M * K));
-  HIP_CHECK(hipMalloc(&dB, sizeof(uint16_t) * K * N));
-  HIP_CHECK(hipMalloc(&dD, sizeof(float) * M * N));
-  HIP_CHECK(hipMemcpy(dA, hA.data(), sizeof(uint16_t) * M * K, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dB, hB.data(), sizeof(uint16_t) * K * N, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_bf16_16x16x32_kernel, dim3(1), dim3(64), 0, 0,
-                     (const __bf16*)dA, (const __bf16*)dB, dD);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(hD.data(), dD, sizeof(float) * M * N, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(dA));
-  HIP_CHECK(hipFree(dB));
-  HIP_CHECK(hipFree(dD));
-  py::dict out;
-  out["m"] = M;
-  out["n"] = N;
-  out["k"] = K;
-  out["a"] = hAf;  // bf16-quantized values as f32, row-major MxK
-  out["b"] = hBf;  // row-major KxN
-  out["d"] = hD;   // GPU MFMA result, row-major MxN
-  return out;
-}
-
-static double mfma_fp8_check(int device) {
-  HIP_CHECK(hipSetDevice(device));
-  const int M = 16, N = 16, K = 32;
-  std::vector<uint8_t> hA(M * K), hB(K * N);
-  std::vector<float> hD(M * N), ref(M * N);
-  for (int i = 0; i < M * K; ++i)
-    hA[i] = encode_e4m3fn_nearest(0.05f * (float)((i * 5) % 23) - 0.5f);
-  for (int i = 0; i < K * N; ++i)
-    hB[i] = encode_e4m3fn_nearest(0.03f * (float)((i * 7) % 19) - 0.25f);
-  for (int m = 0; m < M; ++m)
-    for (int n = 0; n < N; ++n) {
-      float acc = 0.f;
-      for (int k = 0; k < K; ++k)
-        acc = fmaf(decode_e4m3fn(hA[m * K + k]), decode_e4m3fn(hB[k * N + n]), acc);
-      ref[m * N + n] = acc;
-    }
-  uint8_t *dA, *dB;
-  float* dD;
-  HIP_CHECK(hipMalloc(&dA, M * K));
-  HIP_CHECK(hipMalloc(&dB, K * N));
-  HIP_CHECK(hipMalloc(&dD, sizeof(float) * M * N));
-  HIP_CHECK(hipMemcpy(dA, hA.data(), M * K, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dB, hB.data(), K * N, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_fp8_16x16x32_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dD);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(hD.data(), dD, sizeof(float) * M * N, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(dA));
-  HIP_CHECK(hipFree(dB));
-  HIP_CHECK(hipFree(dD));
-  double max_err = 0.0;
-  for (int i = 0; i < M * N; ++i)
-    max_err = std::max(max_err, (double)std::fabs(hD[i] - ref[i]));
-  return max_err;
-}
-
 // ---------------------------------------------------------------------------
 // Matrix-core throughput burn-in: sustained back-to-back
 // v_mfma_f32_16x16x32_bf16 with 4 independent accumulators per wave
@@ -289,38 +176,19 @@ __global__ void mfma_burn_kernel(const __bf16* __restrict__ seed,
 
 static double mfma_throughput_tflops(int device, int iters) {
   HIP_CHECK(hipSetDevice(device));
-  // tiny bf16 operands around 1e-3 so accumulators stay finite
-  std::vector<uint16_t> hseed(256);
-  for (int i = 0; i < 256; ++i) {
-    float f = 0.001f + 0.00001f * (float)(i % 17);
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    hseed[i] = (uint16_t)(u >> 16);
-  }
+  const std::vector<uint16_t> hseed = bf16_burn_seed();
   const int block = 256, grid = 1024;  // 4096 waves = 4 per SIMD
-  uint16_t* dseed;
-  float* dout;
-  HIP_CHECK(hipMalloc(&dseed, sizeof(uint16_t) * 256));
-  HIP_CHECK(hipMalloc(&dout, sizeof(float) * block * grid));
-  HIP_CHECK(hipMemcpy(dseed, hseed.data(), sizeof(uint16_t) * 256,
-                      hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_burn_kernel, dim3(grid), dim3(block), 0, 0,
-                     (const __bf16*)dseed, dout, 1000);  // warmup
+  DeviceBuf<uint16_t> dseed(hseed.size());
+  DeviceBuf<float> dout((size_t)block * grid);
+  dseed.upload(hseed.data(), hseed.size());
+  auto launch = [&](int n) {
+    hipLaunchKernelGGL(mfma_burn_kernel, dim3(grid), dim3(block), 0, 0,
+                       (const __bf16*)dseed.get(), dout.get(), n);
+  };
+  launch(1000);  // warmup
   HIP_CHECK(hipDeviceSynchronize());
-  hipEvent_t t0, t1;
-  HIP_CHECK(hipEventCreate(&t0));
-  HIP_CHECK(hipEventCreate(&t1));
-  HIP_CHECK(hipEventRecord(t0));
-  hipLaunchKernelGGL(mfma_burn_kernel, dim3(grid), dim3(block), 0, 0,
-                     (const __bf16*)dseed, dout, iters);
-  HIP_CHECK(hipEventRecord(t1));
-  HIP_CHECK(hipEventSynchronize(t1));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-  HIP_CHECK(hipEventDestroy(t0));
-  HIP_CHECK(hipEventDestroy(t1));
-  HIP_CHECK(hipFree(dseed));
-  HIP_CHECK(hipFree(dout));
+  EventTimer timer;
+  const float ms = timer.time_ms([&] { launch(iters); });
   const double waves = (double)grid * block / 64.0;
   const double flop = waves * (double)iters * 4.0 * (16.0 * 16.0 * 32.0 * 2.0);
   return flop / 1e12 / ((double)ms / 1e3);
@@ -392,86 +260,62 @@ static py::dict device_probe(int device) {
   return d;
 }
 
+// One wave runs one of the three smoke kernels on a 16xK by Kx16 problem and
+// returns the 16x16 tile.  T is the host type of an encoded element, KT the
+// type the kernel reads it as.
+template <typename T, typename KT>
+static std::vector<float> run_single_wave_tile(
+    const std::vector<T>& a, const std::vector<T>& b,
+    void (*kernel)(const KT*, const KT*, float*)) {
+  static_assert(sizeof(T) == sizeof(KT), "encoded element size");
+  DeviceBuf<T> dA(a.size()), dB(b.size());
+  DeviceBuf<float> dD(16 * 16);
+  dA.upload(a.data(), a.size());
+  dB.upload(b.data(), b.size());
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, 0,
+                     reinterpret_cast<const KT*>(dA.get()),
+                     reinterpret_cast<const KT*>(dB.get()), dD.get());
+  HIP_CHECK(hipGetLastError());
+  std::vector<float> d(dD.size());
+  dD.download(d.data(), d.size());
+  return d;
+}
+
 static double mfma_f32_check(int device) {
   HIP_CHECK(hipSetDevice(device));
-  const int M = 16, N = 16, K = 4;
-  std::vector<float> hA(M * K), hB(K * N), hD(M * N), ref(M * N);
-  // asymmetric operands so transposed writes can't pass (guide §3 note)
-  for (int i = 0; i < M * K; ++i) hA[i] = 0.01f * (float)(i % 37) - 0.15f;
-  for (int i = 0; i < K * N; ++i) hB[i] = 0.02f * (float)((i * 7) % 23) - 0.2f;
-  // exact CPU reference: k-ordered fmaf chain (guide: bitwise equal)
-  for (int m = 0; m < M; ++m)
-    for (int n = 0; n < N; ++n) {
-      float acc = 0.f;
-      for (int k = 0; k < K; ++k) acc = fmaf(hA[m * K + k], hB[k * N + n], acc);
-      ref[m * N + n] = acc;
-    }
-  float *dA, *dB, *dD;
-  HIP_CHECK(hipMalloc(&dA, sizeof(float) * M * K));
-  HIP_CHECK(hipMalloc(&dB, sizeof(float) * K * N));
-  HIP_CHECK(hipMalloc(&dD, sizeof(float) * M * N));
-  HIP_CHECK(hipMemcpy(dA, hA.data(), sizeof(float) * M * K, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dB, hB.data(), sizeof(float) * K * N, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_f32_16x16x4_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dD);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(hD.data(), dD, sizeof(float) * M * N, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(dA));
-  HIP_CHECK(hipFree(dB));
-  HIP_CHECK(hipFree(dD));
-  double max_err = 0.0;
-  for (int i = 0; i < M * N; ++i)
-    max_err = std::max(max_err, (double)std::fabs(hD[i] - ref[i]));
-  return max_err;
+  const SmokeTile<float> t = smoke_f32_problem();
+  return max_abs_err(
+      run_single_wave_tile(t.a_enc, t.b_enc, mfma_f32_16x16x4_kernel), t.ref);
 }
 
 static double mfma_bf16_check(int device) {
   HIP_CHECK(hipSetDevice(device));
-  const int M = 16, N = 16, K = 32;
-  std::vector<float> hAf(M * K), hBf(K * N), hD(M * N), ref(M * N);
-  std::vector<uint16_t> hA(M * K), hB(K * N);
-  auto to_bf16 = [](float f) -> uint16_t {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    // round-to-nearest-even truncation
-    uint32_t rounded = u + 0x7FFF + ((u >> 16) & 1);
-    return (uint16_t)(rounded >> 16);
-  };
-  auto from_bf16 = [](uint16_t v) -> float {
-    uint32_t u = (uint32_t)v << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-  };
-  for (int i = 0; i < M * K; ++i) hAf[i] = 0.03f * (float)((i * 3) % 29) - 0.4f;
-  for (int i = 0; i < K * N; ++i) hBf[i] = 0.015f * (float)((i * 11) % 31) - 0.2f;
-  for (int i = 0; i < M * K; ++i) hA[i] = to_bf16(hAf[i]);
-  for (int i = 0; i < K * N; ++i) hB[i] = to_bf16(hBf[i]);
-  // f32 CPU reference over the bf16-quantized operands
-  for (int m = 0; m < M; ++m)
-    for (int n = 0; n < N; ++n) {
-      float acc = 0.f;
-      for (int k = 0; k < K; ++k)
-        acc = fmaf(from_bf16(hA[m * K + k]), from_bf16(hB[k * N + n]), acc);
-      ref[m * N + n] = acc;
-    }
-  uint16_t *dA, *dB;
-  float* dD;
-  HIP_CHECK(hipMalloc(&dA, sizeof(uint16_t) * M * K));
-  HIP_CHECK(hipMalloc(&dB, sizeof(uint16_t) * K * N));
-  HIP_CHECK(hipMalloc(&dD, sizeof(float) * M * N));
-  HIP_CHECK(hipMemcpy(dA, hA.data(), sizeof(uint16_t) * M * K, hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemcpy(dB, hB.data(), sizeof(uint16_t) * K * N, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_bf16_16x16x32_kernel, dim3(1), dim3(64), 0, 0,
-                     (const __bf16*)dA, (const __bf16*)dB, dD);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(hD.data(), dD, sizeof(float) * M * N, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(dA));
-  HIP_CHECK(hipFree(dB));
-  HIP_CHECK(hipFree(dD));
-  double max_err = 0.0;
-  for (int i = 0; i < M * N; ++i)
-    max_err = std::max(max_err, (double)std::fabs(hD[i] - ref[i]));
-  return max_err;
+  const SmokeTile<uint16_t> t = smoke_bf16_problem();
+  return max_abs_err(
+      run_single_wave_tile(t.a_enc, t.b_enc, mfma_bf16_16x16x32_kernel), t.ref);
+}
+
+static double mfma_fp8_check(int device) {
+  HIP_CHECK(hipSetDevice(device));
+  const SmokeTile<uint8_t> t = smoke_fp8_problem();
+  return max_abs_err(
+      run_single_wave_tile(t.a_enc, t.b_enc, mfma_fp8_16x16x32_kernel), t.ref);
+}
+
+static py::dict mfma_bf16_tile(int device) {
+  // Run the bf16 MFMA tile and return decoded inputs + GPU output so Python
+  // tests can verify against an independent fp32 reference (e.g. torch).
+  HIP_CHECK(hipSetDevice(device));
+  const SmokeTile<uint16_t> t = smoke_bf16_tile_problem();
+  py::dict out;
+  out["m"] = 16;
+  out["n"] = 16;
+  out["k"] = t.k;
+  out["a"] = t.a_dec;  // bf16-quantized values as f32, row-major MxK
+  out["b"] = t.b_dec;  // row-major KxN
+  // GPU MFMA result, row-major MxN
+  out["d"] = run_single_wave_tile(t.a_enc, t.b_enc, mfma_bf16_16x16x32_kernel);
+  return out;
 }
 
 static double hbm_bandwidth_gbps(int device, double buf_mib, int iters) {
@@ -479,32 +323,23 @@ static double hbm_bandwidth_gbps(int device, double buf_mib, int iters) {
   size_t bytes = (size_t)(buf_mib * 1024.0 * 1024.0);
   size_t n = bytes / sizeof(float4);
   bytes = n * sizeof(float4);
-  float4 *src, *dst;
-  HIP_CHECK(hipMalloc(&src, bytes));
-  HIP_CHECK(hipMalloc(&dst, bytes));
-  HIP_CHECK(hipMemset(src, 1, bytes));
+  DeviceBuf<float4> src(n), dst(n);
+  src.fill(1);
   // sweep-tuned launch shape (see header comment): block 512, grid scaled to
   // ~2 float4 per thread, capped at the sweep's best 131072
   int block = 512;
   long want = (long)(n / (2 * (size_t)block)) + 1;
   int grid = (int)std::min<long>(131072, std::max<long>(1024, want));
-  hipEvent_t t0, t1;
-  HIP_CHECK(hipEventCreate(&t0));
-  HIP_CHECK(hipEventCreate(&t1));
-  // warmup
-  hipLaunchKernelGGL(bw_copy_kernel, dim3(grid), dim3(block), 0, 0, src, dst, n);
+  auto launch = [&] {
+    hipLaunchKernelGGL(bw_copy_kernel, dim3(grid), dim3(block), 0, 0, src.get(),
+                       dst.get(), n);
+  };
+  EventTimer timer;
+  launch();  // warmup
   HIP_CHECK(hipDeviceSynchronize());
-  HIP_CHECK(hipEventRecord(t0));
-  for (int i = 0; i < iters; ++i)
-    hipLaunchKernelGGL(bw_copy_kernel, dim3(grid), dim3(block), 0, 0, src, dst, n);
-  HIP_CHECK(hipEventRecord(t1));
-  HIP_CHECK(hipEventSynchronize(t1));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-  HIP_CHECK(hipEventDestroy(t0));
-  HIP_CHECK(hipEventDestroy(t1));
-  HIP_CHECK(hipFree(src));
-  HIP_CHECK(hipFree(dst));
+  const float ms = timer.time_ms([&] {
+    for (int i = 0; i < iters; ++i) launch();
+  });
   // read + write
   double gb = 2.0 * (double)bytes * iters / 1e9;
   return gb / ((double)ms / 1e3);
@@ -515,15 +350,12 @@ static bool lds_roundtrip_check(int device) {
   const int blocks = 512, n = blocks * 1024;
   std::vector<float> hin(n), hout(n);
   for (int i = 0; i < n; ++i) hin[i] = (float)(i % 977) * 0.5f;
-  float *din, *dout;
-  HIP_CHECK(hipMalloc(&din, sizeof(float) * n));
-  HIP_CHECK(hipMalloc(&dout, sizeof(float) * n));
-  HIP_CHECK(hipMemcpy(din, hin.data(), sizeof(float) * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(lds_roundtrip_kernel, dim3(blocks), dim3(256), 0, 0, din, dout, n);
+  DeviceBuf<float> din(n), dout(n);
+  din.upload(hin.data(), n);
+  hipLaunchKernelGGL(lds_roundtrip_kernel, dim3(blocks), dim3(256), 0, 0,
+                     din.get(), dout.get(), n);
   HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipMemcpy(hout.data(), dout, sizeof(float) * n, hipMemcpyDeviceToHost));
-  HIP_CHECK(hipFree(din));
-  HIP_CHECK(hipFree(dout));
+  dout.download(hout.data(), n);
   for (int i = 0; i < n; ++i)
     if (hout[i] != hin[i] * 2.0f) return false;
   return true;
@@ -559,37 +391,36 @@ static py::list xgmi_p2p_probe(int device, double buf_mib, int iters) {
       out.append(entry);
       continue;
     }
-    void* src = nullptr;
-    void* dst = nullptr;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipMalloc(&src, bytes));
-    HIP_CHECK(hipMemset(src, 1, bytes));
+    // dst lives on the peer: it is freed below while the peer is selected.
+    // Only when something throws does its destructor free it under whichever
+    // device is current.
+    DeviceBuf<uint8_t> dst;
+    {
+      HIP_CHECK(hipSetDevice(device));
+      DeviceBuf<uint8_t> src(bytes);
+      src.fill(1);
+      HIP_CHECK(hipSetDevice(peer));
+      dst = DeviceBuf<uint8_t>(bytes);
+      HIP_CHECK(hipSetDevice(device));
+      EventTimer timer;
+      auto copy = [&] {
+        HIP_CHECK(hipMemcpyPeer(dst.get(), peer, src.get(), device, bytes));
+      };
+      copy();  // warmup
+      HIP_CHECK(hipDeviceSynchronize());
+      const float ms = timer.time_ms([&] {
+        for (int i = 0; i < iters; ++i) copy();
+      });
+      entry["bandwidth_gbps"] = ((double)bytes * iters / 1e9) / ((double)ms / 1e3);
+    }
     HIP_CHECK(hipSetDevice(peer));
-    HIP_CHECK(hipMalloc(&dst, bytes));
-    HIP_CHECK(hipSetDevice(device));
-    hipEvent_t t0, t1;
-    HIP_CHECK(hipEventCreate(&t0));
-    HIP_CHECK(hipEventCreate(&t1));
-    HIP_CHECK(hipMemcpyPeer(dst, peer, src, device, bytes));  // warmup
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipEventRecord(t0));
-    for (int i = 0; i < iters; ++i)
-      HIP_CHECK(hipMemcpyPeer(dst, peer, src, device, bytes));
-    HIP_CHECK(hipEventRecord(t1));
-    HIP_CHECK(hipEventSynchronize(t1));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0, t1));
-    entry["bandwidth_gbps"] = ((double)bytes * iters / 1e9) / ((double)ms / 1e3);
-    HIP_CHECK(hipEventDestroy(t0));
-    HIP_CHECK(hipEventDestroy(t1));
-    HIP_CHECK(hipFree(src));
-    HIP_CHECK(hipSetDevice(peer));
-    HIP_CHECK(hipFree(dst));
+    dst.reset();
     HIP_CHECK(hipSetDevice(device));
     out.append(entry);
   }
   return out;
 }
+
 
 // ---------------------------------------------------------------------------
 // Per-CU coverage sweep.  The single-wave MFMA smokes above exercise one
@@ -616,7 +447,6 @@ static py::list xgmi_p2p_probe(int device, double buf_mib, int iters) {
 // makes one round the normal case; the host relaunches (bounded) otherwise.
 // ---------------------------------------------------------------------------
 
-constexpr int kCovSets = 4;                 // operand sets per repetition
 constexpr int kCovLdsWords = 16384;         // 64 KiB static LDS per workgroup
 constexpr int kCovKeys = 4096;              // 4 XCC bits + 8 HW_ID bits
 constexpr int kCovSlots = kCovKeys * 4;     // x 4 SIMDs
@@ -628,16 +458,6 @@ constexpr unsigned kCovFailF32 = 1u, kCovFailBf16 = 2u, kCovFailFp8 = 4u,
 // s_getreg simm16 = id | offset << 6 | (size - 1) << 11; full 32 bits of each.
 constexpr int kCovHwRegHwId = 4 | (31 << 11);
 constexpr int kCovHwRegXccId = 20 | (31 << 11);
-
-// Per-lane record of one operand set, already in MFMA fragment order (the
-// layouts documented on the three smoke kernels above), packed by the host.
-struct CovLaneRec {
-  uint32_t f32_a, f32_b;        // A[l&15][l>>4], B[l>>4][l&15]
-  uint32_t bf16_a[4], bf16_b[4];  // 8 bf16: A[l&15][(l>>4)*8+i], B[(l>>4)*8+i][l&15]
-  uint32_t fp8_a[2], fp8_b[2];  // 8 e4m3, same geometry as bf16
-  uint32_t exp[3][4];           // expected D[(l>>4)*4+r][l&15] bits per dtype
-};
-constexpr int kCovRecWords = sizeof(CovLaneRec) / sizeof(uint32_t);
 
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 
@@ -725,110 +545,6 @@ cu_coverage_kernel(const uint32_t* tab, uint32_t* __restrict__ slot_waves,
 #endif
 }
 
-// Integer operand generators: |v| <= 8, A and B unrelated (a transposed
-// fragment cannot pass), every (set, dtype) pair a different pattern.
-static int cov_a_val(int set, int dt, int m, int k) {
-  return (m * 3 + k * 5 + set * 7 + dt * 2 + (m * k) % 5) % 17 - 8;
-}
-static int cov_b_val(int set, int dt, int k, int n) {
-  return (k * 7 + n * 11 + set * 13 + dt * 4 + 3 + (k * n) % 7) % 17 - 8;
-}
-
-static uint16_t cov_to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return (uint16_t)((u + 0x7FFF + ((u >> 16) & 1)) >> 16);
-}
-static float cov_from_bf16(uint16_t v) {
-  uint32_t u = (uint32_t)v << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-static uint32_t cov_f32_bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  return u;
-}
-
-// One (set, dtype) problem: encoded operands, their decoded f32 values and
-// the expected tile, which is computed in integers from the intended values
-// (not from the decoded ones, so an encoding that fails to round-trip shows).
-struct CovProblem {
-  int k;
-  std::vector<uint32_t> a_enc, b_enc;  // f32 bits / bf16 / e4m3 code per element
-  std::vector<float> a_dec, b_dec, d;  // row-major 16xK, Kx16, 16x16
-};
-
-static const char* const kCovDtypeNames[3] = {"f32", "bf16", "fp8"};
-
-static CovProblem cov_problem(int set, int dt) {
-  CovProblem p;
-  p.k = dt == 0 ? 4 : 32;
-  const int K = p.k;
-  std::vector<int> a(16 * K), b(K * 16);
-  for (int m = 0; m < 16; ++m)
-    for (int k = 0; k < K; ++k) a[m * K + k] = cov_a_val(set, dt, m, k);
-  for (int k = 0; k < K; ++k)
-    for (int n = 0; n < 16; ++n) b[k * 16 + n] = cov_b_val(set, dt, k, n);
-  auto encode = [dt](int v, uint32_t* enc, float* dec) {
-    const float f = (float)v;
-    if (dt == 0) {
-      *enc = cov_f32_bits(f);
-      *dec = f;
-    } else if (dt == 1) {
-      const uint16_t h = cov_to_bf16(f);
-      *enc = h;
-      *dec = cov_from_bf16(h);
-    } else {
-      const uint8_t q = encode_e4m3fn_nearest(f);
-      *enc = q;
-      *dec = decode_e4m3fn(q);
-    }
-  };
-  p.a_enc.resize(16 * K);
-  p.a_dec.resize(16 * K);
-  p.b_enc.resize(K * 16);
-  p.b_dec.resize(K * 16);
-  for (int i = 0; i < 16 * K; ++i) encode(a[i], &p.a_enc[i], &p.a_dec[i]);
-  for (int i = 0; i < K * 16; ++i) encode(b[i], &p.b_enc[i], &p.b_dec[i]);
-  p.d.resize(256);
-  for (int m = 0; m < 16; ++m)
-    for (int n = 0; n < 16; ++n) {
-      int acc = 0;
-      for (int k = 0; k < K; ++k) acc += a[m * K + k] * b[k * 16 + n];
-      p.d[m * 16 + n] = (float)acc;
-    }
-  return p;
-}
-
-// Pack every set into per-lane fragment records for the kernel.
-static std::vector<uint32_t> cov_build_table() {
-  std::vector<uint32_t> tab((size_t)kCovSets * 64 * kCovRecWords, 0u);
-  for (int s = 0; s < kCovSets; ++s) {
-    CovProblem pr[3] = {cov_problem(s, 0), cov_problem(s, 1), cov_problem(s, 2)};
-    for (int l = 0; l < 64; ++l) {
-      CovLaneRec rec;
-      std::memset(&rec, 0, sizeof(rec));
-      const int lo = l & 15, hi = l >> 4;
-      rec.f32_a = pr[0].a_enc[lo * 4 + hi];
-      rec.f32_b = pr[0].b_enc[hi * 16 + lo];
-      for (int i = 0; i < 8; ++i) {
-        const int k = hi * 8 + i;
-        rec.bf16_a[i / 2] |= pr[1].a_enc[lo * 32 + k] << (16 * (i & 1));
-        rec.bf16_b[i / 2] |= pr[1].b_enc[k * 16 + lo] << (16 * (i & 1));
-        rec.fp8_a[i / 4] |= pr[2].a_enc[lo * 32 + k] << (8 * (i & 3));
-        rec.fp8_b[i / 4] |= pr[2].b_enc[k * 16 + lo] << (8 * (i & 3));
-      }
-      for (int t = 0; t < 3; ++t)
-        for (int r = 0; r < 4; ++r)
-          rec.exp[t][r] = cov_f32_bits(pr[t].d[(hi * 4 + r) * 16 + lo]);
-      std::memcpy(&tab[(size_t)(s * 64 + l) * kCovRecWords], &rec, sizeof(rec));
-    }
-  }
-  return tab;
-}
-
 static py::dict cu_coverage_reference() {
   // host only: no HIP call
   py::dict out;
@@ -850,30 +566,6 @@ static py::dict cu_coverage_reference() {
   }
   return out;
 }
-
-// RAII holders local to the sweep: nothing leaks when HIP_CHECK throws.
-struct CovDeviceBuf {
-  void* ptr = nullptr;
-  CovDeviceBuf() = default;
-  CovDeviceBuf(const CovDeviceBuf&) = delete;
-  CovDeviceBuf& operator=(const CovDeviceBuf&) = delete;
-  ~CovDeviceBuf() {
-    if (ptr) (void)hipFree(ptr);
-  }
-  void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&ptr, bytes)); }
-  uint32_t* u32() const { return static_cast<uint32_t*>(ptr); }
-};
-
-struct CovEvent {
-  hipEvent_t ev = nullptr;
-  CovEvent() = default;
-  CovEvent(const CovEvent&) = delete;
-  CovEvent& operator=(const CovEvent&) = delete;
-  ~CovEvent() {
-    if (ev) (void)hipEventDestroy(ev);
-  }
-  void create() { HIP_CHECK(hipEventCreate(&ev)); }
-};
 
 // The host side of a whole-device sweep, shared by cu_coverage_check and
 // mx_coverage_check: argument validation before the first HIP call, table
@@ -905,18 +597,13 @@ static py::dict cov_run_sweep(const std::string& who, int device, int reps,
     throw std::runtime_error(
         who + ": device grants less than 64 KiB of LDS per workgroup");
 
-  const size_t slot_bytes = sizeof(uint32_t) * kCovSlots;
-  CovDeviceBuf d_tab, d_slots;  // d_slots: waves | fail | hw_id | xcc_id
-  d_tab.alloc(sizeof(uint32_t) * tab.size());
-  d_slots.alloc(4 * slot_bytes);
-  HIP_CHECK(hipMemcpy(d_tab.ptr, tab.data(), sizeof(uint32_t) * tab.size(),
-                      hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemset(d_slots.ptr, 0, 4 * slot_bytes));
-  CovEvent t0, t1;
-  t0.create();
-  t1.create();
+  DeviceBuf<uint32_t> d_tab(tab.size());
+  DeviceBuf<uint32_t> d_slots((size_t)4 * kCovSlots);  // waves | fail | hw_id | xcc_id
+  d_tab.upload(tab.data(), tab.size());
+  d_slots.fill(0);
+  EventTimer timer;
 
-  std::vector<uint32_t> h((size_t)4 * kCovSlots);
+  std::vector<uint32_t> h(d_slots.size());
   const uint32_t* h_waves = h.data();
   const uint32_t* h_fail = h.data() + kCovSlots;
   const uint32_t* h_hw = h.data() + 2 * kCovSlots;
@@ -924,17 +611,12 @@ static py::dict cov_run_sweep(const std::string& who, int device, int reps,
   int rounds = 0, cus_covered = 0, slots_covered = 0;
   double elapsed_ms = 0.0;
   while (rounds < max_rounds) {
-    HIP_CHECK(hipEventRecord(t0.ev));
-    launch(cus, d_tab.u32(), d_slots.u32());
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(t1.ev));
-    HIP_CHECK(hipEventSynchronize(t1.ev));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
-    elapsed_ms += ms;
+    elapsed_ms += timer.time_ms([&] {
+      launch(cus, d_tab.get(), d_slots.get());
+      HIP_CHECK(hipGetLastError());
+    });
     ++rounds;
-    HIP_CHECK(hipMemcpy(h.data(), d_slots.ptr, 4 * slot_bytes,
-                        hipMemcpyDeviceToHost));
+    d_slots.download(h.data(), h.size());
     cus_covered = slots_covered = 0;
     for (int key = 0; key < kCovKeys; ++key) {
       int simds = 0;
@@ -1026,287 +708,6 @@ static py::dict cu_coverage_check(int device, int reps, int max_rounds,
 // throws otherwise; the comparison is bitwise, with no tolerance.
 // ---------------------------------------------------------------------------
 
-constexpr int kMxFormats = 5;
-constexpr int kMxSets = 5;
-constexpr int kMxSpanBoundLog2 = 20;
-
-struct MxFormat {
-  const char* name;
-  int bits, ebits, mbits, bias;
-  int unit;      // alphabet values are mags[i] * 2^unit
-  int n_mags;
-  int mags[16];  // both signs of each are used
-  bool zero;     // plus zero
-};
-
-// Alphabets: both signs, every mantissa bit pattern, at least three exponent
-// values, magnitudes small enough for the span bound.  e2m1: all 15 values.
-static const MxFormat kMxFmt[kMxFormats] = {
-    {"e4m3", 8, 4, 3, 7, -3, 13, {1, 2, 3, 5, 8, 9, 10, 11, 12, 13, 14, 15, 16}, false},
-    {"e5m2", 8, 5, 2, 15, -2, 11, {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14}, false},
-    {"e2m3", 6, 2, 3, 1, -3, 16,
-     {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16}, false},
-    {"e3m2", 6, 3, 2, 3, -4, 12, {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16}, false},
-    {"e2m1", 4, 2, 1, 1, -1, 7, {1, 2, 3, 4, 6, 8, 12}, true},
-};
-
-// A code as (-1)^sign * mant * 2^exp; NaN / Inf codes are not finite.
-struct MxParts {
-  bool finite;
-  int sign, mant, exp;
-};
-
-static MxParts mx_decode_parts(int fmt, unsigned code) {
-  const MxFormat& f = kMxFmt[fmt];
-  const int e = (code >> f.mbits) & ((1 << f.ebits) - 1);
-  const int m = code & ((1 << f.mbits) - 1);
-  MxParts p{true, (int)((code >> (f.bits - 1)) & 1u), 0, 0};
-  if (fmt == 0 && e == 15 && m == 7) p.finite = false;  // e4m3 NaN
-  if (fmt == 1 && e == 31) p.finite = false;            // e5m2 Inf / NaN
-  if (e == 0) {
-    p.mant = m;  // subnormal
-    p.exp = 1 - f.bias - f.mbits;
-  } else {
-    p.mant = (1 << f.mbits) + m;
-    p.exp = e - f.bias - f.mbits;
-  }
-  return p;
-}
-
-static double mx_decode(int fmt, unsigned code) {
-  const MxParts p = mx_decode_parts(fmt, code);
-  const double v = std::ldexp((double)p.mant, p.exp);
-  return p.sign ? -v : v;
-}
-
-// Exact encoder of n * 2^unit: throws when no finite code has that value.
-static uint8_t mx_encode_exact(int fmt, int n, int unit) {
-  if (n == 0) return 0;
-  const int mag = n < 0 ? -n : n;
-  for (unsigned code = 0; code < (1u << kMxFmt[fmt].bits); ++code) {
-    const MxParts p = mx_decode_parts(fmt, code);
-    if (!p.finite || p.mant == 0 || p.sign != (n < 0)) continue;
-    const int d = p.exp - unit;
-    if (d >= 0 ? (d < 24 && (p.mant << d) == mag)
-               : (-d < 24 && (mag << -d) == p.mant))
-      return (uint8_t)code;
-  }
-  throw std::domain_error(std::string("mx_encode_exact: ") + kMxFmt[fmt].name +
-                          " cannot represent " + std::to_string(n) + " * 2^" +
-                          std::to_string(unit));
-}
-
-// E8M0: 2^(code - 127); 0xFF is NaN and never produced.
-static uint8_t mx_encode_e8m0(int exp) {
-  if (exp < -127 || exp > 127)
-    throw std::domain_error("mx_encode_e8m0: 2^" + std::to_string(exp) +
-                            " has no E8M0 code");
-  return (uint8_t)(exp + 127);
-}
-static double mx_decode_e8m0(uint8_t code) {
-  return std::ldexp(1.0, (int)code - 127);
-}
-
-// op_sel byte of the scale VGPR, per set: A and B use different bytes
-constexpr int mx_sel_a(int set) { return set & 3; }
-constexpr int mx_sel_b(int set) { return set == 0 ? 0 : 1 + (set % 3); }
-// scale exponents per set are base + one of three offsets: set 0 uniform, 1
-// and 2 near one, 3 far apart, 4 a wider spread that takes S/q near the bound
-static const int kMxScaleBaseA[kMxSets] = {0, -1, 2, 20, -2};
-static const int kMxScaleBaseB[kMxSets] = {0, 0, -3, -21, -1};
-static const int kMxScaleSpread[kMxSets][3] = {
-    {0, 0, 0}, {0, 1, 2}, {0, 1, 2}, {0, 1, 2}, {0, 1, 3}};
-
-struct MxProblem {
-  int set, fa, fb, shape;  // shape 0: 16x16x128, 1: 32x32x64
-  int m, n, k, kblocks, sel_a, sel_b;
-  std::vector<uint8_t> a_codes, b_codes;    // row-major m x k, k x n
-  std::vector<uint8_t> a_scales, b_scales;  // row-major m x kblocks, kblocks x n
-  std::vector<float> d;                     // expected, row-major m x n
-  double log2_span;                         // achieved log2(S / q)
-  std::vector<uint32_t> a_words, b_words;   // 64 lanes x 8 operand words
-  std::vector<uint32_t> a_scale_words, b_scale_words;  // 64 lanes
-};
-
-static const char* mx_shape_name(int shape) {
-  return shape == 0 ? "16x16x128" : "32x32x64";
-}
-
-// K index of element j of a lane in lane group g (see the layout above)
-static int mx_lane_k(int bits, int K, int g, int j) {
-  return bits == 8 ? (K / 2) * (j >> 4) + 16 * g + (j & 15) : 32 * g + j;
-}
-
-// One lane's 32 elements of row / col `codes` (K elements, `stride` apart):
-// element j at bits [w*j, w*j + w) of 8 words
-static void mx_pack_lane(int bits, int K, int g, const uint8_t* codes,
-                         size_t stride, uint32_t* words) {
-  for (int i = 0; i < 8; ++i) words[i] = 0;
-  for (int j = 0; j < 32; ++j) {
-    const uint32_t c = codes[mx_lane_k(bits, K, g, j) * stride];
-    const int pos = j * bits, w = pos >> 5, off = pos & 31;
-    words[w] |= c << off;
-    if (off + bits > 32) words[w + 1] |= c >> (32 - off);
-  }
-}
-
-static int mx_ctz(int64_t v) {
-  int z = 0;
-  while ((v & 1) == 0) {
-    v >>= 1;
-    ++z;
-  }
-  return z;
-}
-
-static MxProblem mx_problem(int set, int fa, int fb, int shape) {
-  if (set < 0 || set >= kMxSets)
-    throw std::invalid_argument("mx_problem: set out of range");
-  if (fa < 0 || fa >= kMxFormats || fb < 0 || fb >= kMxFormats)
-    throw std::invalid_argument("mx_problem: unknown format");
-  if (shape != 0 && shape != 1)
-    throw std::invalid_argument("mx_problem: unknown shape");
-  MxProblem p;
-  p.set = set;
-  p.fa = fa;
-  p.fb = fb;
-  p.shape = shape;
-  p.m = p.n = shape == 0 ? 16 : 32;
-  p.k = shape == 0 ? 128 : 64;
-  p.kblocks = p.k / 32;
-  p.sel_a = mx_sel_a(set);
-  p.sel_b = mx_sel_b(set);
-  const int M = p.m, N = p.n, K = p.k, KB = p.kblocks;
-
-  auto alphabet = [](int fmt) {
-    const MxFormat& f = kMxFmt[fmt];
-    std::vector<int> v;
-    for (int i = 0; i < f.n_mags; ++i) {
-      v.push_back(f.mags[i]);
-      v.push_back(-f.mags[i]);
-    }
-    if (f.zero) v.push_back(0);
-    return v;
-  };
-  const std::vector<int> al_a = alphabet(fa), al_b = alphabet(fb);
-  const int ua = kMxFmt[fa].unit, ub = kMxFmt[fb].unit;
-
-  // intended values (integers in units of 2^ua, 2^ub) and scale exponents;
-  // A and B are unrelated patterns and every (set, pair, shape) differs
-  std::vector<int> a(M * K), b(K * N), sa(M * KB), sb(KB * N);
-  for (int m = 0; m < M; ++m)
-    for (int k = 0; k < K; ++k)
-      a[m * K + k] = al_a[(m * 3 + k * 5 + set * 7 + fa * 2 + fb * 3 +
-                           shape * 11 + (m * k) % 5) % (int)al_a.size()];
-  for (int k = 0; k < K; ++k)
-    for (int n = 0; n < N; ++n)
-      b[k * N + n] = al_b[(k * 7 + n * 11 + set * 13 + fb * 4 + fa * 5 +
-                           shape * 3 + 3 + (k * n) % 7) % (int)al_b.size()];
-  // neighbouring rows / cols and neighbouring kblocks get different scales
-  // (set 0 is uniform: it checks the operand maps on their own)
-  for (int m = 0; m < M; ++m)
-    for (int kb = 0; kb < KB; ++kb)
-      sa[m * KB + kb] =
-          kMxScaleBaseA[set] + kMxScaleSpread[set][(m + 2 * kb + set) % 3];
-  for (int kb = 0; kb < KB; ++kb)
-    for (int n = 0; n < N; ++n)
-      sb[kb * N + n] =
-          kMxScaleBaseB[set] + kMxScaleSpread[set][(2 * n + kb + set + 1) % 3];
-
-  // encode; an operand that does not round-trip throws
-  p.a_codes.resize(M * K);
-  p.b_codes.resize(K * N);
-  p.a_scales.resize(M * KB);
-  p.b_scales.resize(KB * N);
-  for (int i = 0; i < M * K; ++i) {
-    p.a_codes[i] = mx_encode_exact(fa, a[i], ua);
-    if (mx_decode(fa, p.a_codes[i]) != std::ldexp((double)a[i], ua))
-      throw std::domain_error("mx_problem: A operand does not round-trip");
-  }
-  for (int i = 0; i < K * N; ++i) {
-    p.b_codes[i] = mx_encode_exact(fb, b[i], ub);
-    if (mx_decode(fb, p.b_codes[i]) != std::ldexp((double)b[i], ub))
-      throw std::domain_error("mx_problem: B operand does not round-trip");
-  }
-  for (int i = 0; i < M * KB; ++i) {
-    p.a_scales[i] = mx_encode_e8m0(sa[i]);
-    if (mx_decode_e8m0(p.a_scales[i]) != std::ldexp(1.0, sa[i]))
-      throw std::domain_error("mx_problem: A scale does not round-trip");
-  }
-  for (int i = 0; i < KB * N; ++i) {
-    p.b_scales[i] = mx_encode_e8m0(sb[i]);
-    if (mx_decode_e8m0(p.b_scales[i]) != std::ldexp(1.0, sb[i]))
-      throw std::domain_error("mx_problem: B scale does not round-trip");
-  }
-
-  // expected tile in 64-bit fixed point with unit 2^e_min, from the intended
-  // integers and exponents (never from decoded floats)
-  int e_min = INT32_MAX;
-  for (int m = 0; m < M; ++m)
-    for (int n = 0; n < N; ++n)
-      for (int kb = 0; kb < KB; ++kb)
-        e_min = std::min(e_min, ua + ub + sa[m * KB + kb] + sb[kb * N + n]);
-  int q_exp = INT32_MAX;  // log2 of q
-  int64_t s_max = 0;      // S in units of 2^e_min
-  p.d.resize(M * N);
-  for (int m = 0; m < M; ++m)
-    for (int n = 0; n < N; ++n) {
-      int64_t acc = 0, abs_sum = 0;
-      for (int k = 0; k < K; ++k) {
-        const int64_t prod = (int64_t)a[m * K + k] * b[k * N + n];
-        if (prod == 0) continue;
-        const int e = ua + ub + sa[m * KB + k / 32] + sb[(k / 32) * N + n];
-        if (e - e_min > 30) throw std::domain_error("mx_problem: scale spread");
-        acc += prod * ((int64_t)1 << (e - e_min));
-        abs_sum += (prod < 0 ? -prod : prod) * ((int64_t)1 << (e - e_min));
-        q_exp = std::min(q_exp, e + mx_ctz(prod));
-      }
-      s_max = std::max(s_max, abs_sum);
-      const double want = std::ldexp((double)acc, e_min);
-      p.d[m * N + n] = (float)want;
-      if ((double)p.d[m * N + n] != want)
-        throw std::domain_error("mx_problem: expected value is not an f32");
-    }
-  if (s_max == 0) throw std::domain_error("mx_problem: empty tile");
-  p.log2_span = std::log2((double)s_max) + (double)(e_min - q_exp);
-  if (p.log2_span > (double)kMxSpanBoundLog2)
-    throw std::domain_error(
-        std::string("mx_problem: S/q = 2^") + std::to_string(p.log2_span) +
-        " exceeds the exactness bound for " + kMxFmt[fa].name + " x " +
-        kMxFmt[fb].name + " " + mx_shape_name(shape) + " set " +
-        std::to_string(set));
-
-  // per-lane fragments; the three scale bytes op_sel does not pick hold valid
-  // scales that would give another answer
-  p.a_words.resize(64 * 8);
-  p.b_words.resize(64 * 8);
-  p.a_scale_words.resize(64);
-  p.b_scale_words.resize(64);
-  for (int l = 0; l < 64; ++l) {
-    const int rc = l % M, kb = l / M;
-    mx_pack_lane(kMxFmt[fa].bits, K, kb, &p.a_codes[rc * K], 1,
-                 &p.a_words[l * 8]);
-    mx_pack_lane(kMxFmt[fb].bits, K, kb, &p.b_codes[rc], (size_t)N,
-                 &p.b_words[l * 8]);
-    const uint32_t ca = p.a_scales[rc * KB + kb], cb = p.b_scales[kb * N + rc];
-    uint32_t wa = 0, wb = 0;
-    for (int i = 0; i < 4; ++i) {
-      wa |= (i == p.sel_a ? ca : ca + 3 + i) << (8 * i);
-      wb |= (i == p.sel_b ? cb : cb + 3 + i) << (8 * i);
-    }
-    p.a_scale_words[l] = wa;
-    p.b_scale_words[l] = wb;
-  }
-  return p;
-}
-
-// The sweep's problems per set: five same-format pairs and three mixed pairs
-// (cbsz != blgp) on 16x16x128, then e2m1 and e4m3 on 32x32x64.
-constexpr int kMxProbs = 10;
-constexpr int kMxProbFa[kMxProbs] = {0, 1, 2, 3, 4, 0, 4, 3, 4, 0};
-constexpr int kMxProbFb[kMxProbs] = {0, 1, 2, 3, 4, 4, 2, 1, 4, 0};
-constexpr int kMxProbShape[kMxProbs] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1};
-constexpr int kMxProbBit[kMxProbs] = {0, 1, 2, 3, 4, 5, 5, 5, 6, 6};
 constexpr int kMxFailBits = 7;  // e4m3 e5m2 e2m3 e3m2 e2m1 mixed shape32
 
 using i32x8 = __attribute__((ext_vector_type(8))) int;
@@ -1328,8 +729,6 @@ __device__ __forceinline__ f32x16 mx32(i32x8 a, i32x8 b, f32x16 c, int sa, int s
 // Single tile: one wave, one instruction.  rec = 64 lanes x {a[8], b[8], sa,
 // sb}; out = 64 lanes x 16 accumulator registers (4 used by 16x16).  The
 // format pair is a run-time argument, so every cbsz / blgp pair has a case.
-constexpr int kMxTileRecWords = 18;
-
 #define MX_TILE_CASE(FN, FA, FB)                                            \
   case FA * kMxFormats + FB:                                                \
     d = FN<FA, FB, mx_sel_a(SET), mx_sel_b(SET)>(a, b, d, sa, sb);          \
@@ -1418,23 +817,11 @@ static py::dict mx_reference() {
 
 template <int SHAPE>
 static void mx_tile_launch(int set, const uint32_t* rec, float* out, int pair) {
-  switch (set) {
-    case 0:
-      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 0>), dim3(1), dim3(64), 0, 0, rec, out, pair);
-      break;
-    case 1:
-      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 1>), dim3(1), dim3(64), 0, 0, rec, out, pair);
-      break;
-    case 2:
-      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 2>), dim3(1), dim3(64), 0, 0, rec, out, pair);
-      break;
-    case 3:
-      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 3>), dim3(1), dim3(64), 0, 0, rec, out, pair);
-      break;
-    default:
-      hipLaunchKernelGGL((mx_tile_kernel<SHAPE, 4>), dim3(1), dim3(64), 0, 0, rec, out, pair);
-      break;
-  }
+  // set is in [0, kMxSets): mx_problem has validated it
+  static void (*const kKernels[kMxSets])(const uint32_t*, float*, int) = {
+      mx_tile_kernel<SHAPE, 0>, mx_tile_kernel<SHAPE, 1>, mx_tile_kernel<SHAPE, 2>,
+      mx_tile_kernel<SHAPE, 3>, mx_tile_kernel<SHAPE, 4>};
+  hipLaunchKernelGGL(kKernels[set], dim3(1), dim3(64), 0, 0, rec, out, pair);
 }
 
 static py::dict mx_mfma_tile(int device, const std::string& fmt_a,
@@ -1445,39 +832,23 @@ static py::dict mx_mfma_tile(int device, const std::string& fmt_a,
   const int fa = mx_format_index(fmt_a), fb = mx_format_index(fmt_b);
   const int sh = mx_shape_index(shape);
   const MxProblem p = mx_problem(set, fa, fb, sh);  // validates set
-  std::vector<uint32_t> rec((size_t)64 * kMxTileRecWords);
-  for (int l = 0; l < 64; ++l) {
-    uint32_t* r = &rec[(size_t)l * kMxTileRecWords];
-    std::memcpy(r, &p.a_words[l * 8], 32);
-    std::memcpy(r + 8, &p.b_words[l * 8], 32);
-    r[16] = p.a_scale_words[l];
-    r[17] = p.b_scale_words[l];
-  }
+  const std::vector<uint32_t> rec = mx_tile_record(p);
   HIP_CHECK(hipSetDevice(device));
-  CovDeviceBuf d_rec, d_out;
-  d_rec.alloc(sizeof(uint32_t) * rec.size());
-  d_out.alloc(sizeof(float) * 64 * 16);
-  HIP_CHECK(hipMemcpy(d_rec.ptr, rec.data(), sizeof(uint32_t) * rec.size(),
-                      hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemset(d_out.ptr, 0xFF, sizeof(float) * 64 * 16));
+  DeviceBuf<uint32_t> d_rec(rec.size());
+  DeviceBuf<float> d_out(64 * 16);
+  d_rec.upload(rec.data(), rec.size());
+  d_out.fill(0xFF);
   if (sh == 0)
-    mx_tile_launch<0>(set, d_rec.u32(), static_cast<float*>(d_out.ptr),
-                      fa * kMxFormats + fb);
+    mx_tile_launch<0>(set, d_rec.get(), d_out.get(), fa * kMxFormats + fb);
   else
-    mx_tile_launch<1>(set, d_rec.u32(), static_cast<float*>(d_out.ptr),
-                      fa * kMxFormats + fb);
+    mx_tile_launch<1>(set, d_rec.get(), d_out.get(), fa * kMxFormats + fb);
   HIP_CHECK(hipGetLastError());
-  std::vector<float> regs(64 * 16);
-  HIP_CHECK(hipMemcpy(regs.data(), d_out.ptr, sizeof(float) * regs.size(),
-                      hipMemcpyDeviceToHost));
+  std::vector<float> regs(d_out.size());
+  d_out.download(regs.data(), regs.size());
   std::vector<float> d_gpu((size_t)p.m * p.n);
   for (int l = 0; l < 64; ++l)
-    for (int r = 0; r < (sh == 0 ? 4 : 16); ++r) {
-      const int row = sh == 0 ? (l >> 4) * 4 + r
-                              : (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-      const int col = sh == 0 ? (l & 15) : (l & 31);
-      d_gpu[row * p.n + col] = regs[l * 16 + r];
-    }
+    for (int r = 0; r < mx_lane_regs(sh); ++r)
+      d_gpu[mx_d_index(sh, l, r)] = regs[l * 16 + r];
   py::dict out = mx_problem_dict(p);
   out["d_gpu"] = d_gpu;  // GPU result, row-major m x n
   return out;
@@ -1487,7 +858,6 @@ static py::dict mx_mfma_tile(int device, const std::string& fmt_a,
 // bounds, 64 KiB LDS claim, placement key and slot scheme, fixed work per
 // workgroup.  Per-lane record of one (set, problem): a[8] b[8] sa sb exp[16]
 // (16x16 problems use exp[0..3]).
-constexpr int kMxRecWords = 34;
 
 template <int SET, int P>
 __device__ __forceinline__ unsigned mx_cov_problem(const uint32_t* tab, int lane,
@@ -1582,29 +952,6 @@ mx_coverage_kernel(const uint32_t* tab, uint32_t* __restrict__ slot_waves,
 #endif
 }
 
-static std::vector<uint32_t> mx_build_table() {
-  std::vector<uint32_t> tab((size_t)kMxSets * kMxProbs * 64 * kMxRecWords, 0u);
-  for (int s = 0; s < kMxSets; ++s)
-    for (int i = 0; i < kMxProbs; ++i) {
-      const MxProblem p =
-          mx_problem(s, kMxProbFa[i], kMxProbFb[i], kMxProbShape[i]);
-      for (int l = 0; l < 64; ++l) {
-        uint32_t* r = &tab[(size_t)((s * kMxProbs + i) * 64 + l) * kMxRecWords];
-        std::memcpy(r, &p.a_words[l * 8], 32);
-        std::memcpy(r + 8, &p.b_words[l * 8], 32);
-        r[16] = p.a_scale_words[l];
-        r[17] = p.b_scale_words[l];
-        for (int q = 0; q < (p.shape == 0 ? 4 : 16); ++q) {
-          const int row = p.shape == 0 ? (l >> 4) * 4 + q
-                                       : (q & 3) + 8 * (q >> 2) + 4 * (l >> 5);
-          const int col = p.shape == 0 ? (l & 15) : (l & 31);
-          r[18 + q] = cov_f32_bits(p.d[row * p.n + col]);
-        }
-      }
-    }
-  return tab;
-}
-
 static py::dict mx_coverage_check(int device, int reps, int max_rounds,
                                   int poison_key, unsigned poison_mask,
                                   bool poison_all) {
@@ -1653,45 +1000,20 @@ static double mx_throughput_tflops(int device, const std::string& fmt, int iters
     throw std::invalid_argument("mx_throughput_tflops: fmt must be e2m1 or e4m3");
   if (iters < 1 || iters > 10000000)
     throw std::invalid_argument("mx_throughput_tflops: iters must be in [1, 1e7]");
-  // 64 lanes x {a[8], b[8]} of non-zero alphabet codes, then the scale word
-  const MxFormat& mf = kMxFmt[f];
-  std::vector<uint32_t> hseed(64 * 16 + 1);
-  for (int l = 0; l < 64; ++l)
-    for (int h = 0; h < 2; ++h) {
-      uint8_t codes[128];  // one row: only the lane's own 32 are read
-      for (int j = 0; j < 128; ++j) {
-        const int mag = mf.mags[(l * 7 + j * 3 + h * 5) % mf.n_mags];
-        codes[j] = mx_encode_exact(f, (l + j + h) % 3 == 0 ? -mag : mag, mf.unit);
-      }
-      mx_pack_lane(mf.bits, 128, l >> 4, codes, 1, &hseed[l * 16 + h * 8]);
-    }
-  hseed[64 * 16] = 0x01010101u * mx_encode_e8m0(-20);
+  const std::vector<uint32_t> hseed = mx_burn_seed(f);
   const int block = 256, grid = 512;  // 2048 waves = 2 per SIMD, 4 chains each
   HIP_CHECK(hipSetDevice(device));
-  CovDeviceBuf d_seed, d_out;
-  d_seed.alloc(sizeof(uint32_t) * hseed.size());
-  d_out.alloc(sizeof(float) * block * grid);
-  HIP_CHECK(hipMemcpy(d_seed.ptr, hseed.data(), sizeof(uint32_t) * hseed.size(),
-                      hipMemcpyHostToDevice));
+  DeviceBuf<uint32_t> d_seed(hseed.size());
+  DeviceBuf<float> d_out((size_t)block * grid);
+  d_seed.upload(hseed.data(), hseed.size());
   auto launch = [&](int n) {
-    if (f == 4)
-      hipLaunchKernelGGL(mx_burn_kernel<4>, dim3(grid), dim3(block), 0, 0,
-                         d_seed.u32(), static_cast<float*>(d_out.ptr), n);
-    else
-      hipLaunchKernelGGL(mx_burn_kernel<0>, dim3(grid), dim3(block), 0, 0,
-                         d_seed.u32(), static_cast<float*>(d_out.ptr), n);
+    hipLaunchKernelGGL(f == 4 ? mx_burn_kernel<4> : mx_burn_kernel<0>, dim3(grid),
+                       dim3(block), 0, 0, d_seed.get(), d_out.get(), n);
   };
   launch(1000);  // warmup
   HIP_CHECK(hipDeviceSynchronize());
-  CovEvent t0, t1;
-  t0.create();
-  t1.create();
-  HIP_CHECK(hipEventRecord(t0.ev));
-  launch(iters);
-  HIP_CHECK(hipEventRecord(t1.ev));
-  HIP_CHECK(hipEventSynchronize(t1.ev));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+  EventTimer timer;
+  const float ms = timer.time_ms([&] { launch(iters); });
   const double waves = (double)grid * block / 64.0;
   const double flop = waves * (double)iters * 4.0 * (16.0 * 16.0 * 128.0 * 2.0);
   return flop / 1e12 / ((double)ms / 1e3);
@@ -1725,7 +1047,6 @@ static double mx_throughput_tflops(int device, const std::string& fmt, int iters
 // fill kernel really wrote.
 // ---------------------------------------------------------------------------
 
-constexpr int kHbmPatternHash = 0, kHbmPatternChecker = 1;
 constexpr int kHbmFill = 0, kHbmVerifyInvert = 1, kHbmVerify = 2;
 constexpr int kHbmBlock = 512;            // bw_copy_kernel's sweep-tuned shape
 constexpr int kHbmShards = 1024;          // compared-word counters, one line each
@@ -1735,17 +1056,6 @@ constexpr int kHbmMaxPasses = 16;
 constexpr size_t kHbmReferenceMax = 65536;
 constexpr uint64_t kHbmReserveBytes = 2ull << 30;
 constexpr uint64_t kHbmBeyondCacheBytes = 512ull << 20;  // 2 x Infinity Cache
-
-// The one definition shared by the kernels and the host reference.
-__host__ __device__ inline uint64_t hbm_pattern_value(int pattern, uint64_t seed,
-                                                      uint64_t i) {
-  if (pattern == kHbmPatternChecker)
-    return (i & 1ull) ? 0x5555555555555555ull : 0xAAAAAAAAAAAAAAAAull;
-  uint64_t z = i + seed * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 using u64x2 = __attribute__((ext_vector_type(2))) uint64_t;
 
@@ -1924,21 +1234,8 @@ static std::vector<uint64_t> hbm_pattern_reference(const std::string& pattern,
   return out;
 }
 
-// RAII holders in the style of CovDeviceBuf / CovEvent.
-struct HbmDeviceBuf {
-  void* ptr = nullptr;
-  HbmDeviceBuf() = default;
-  HbmDeviceBuf(const HbmDeviceBuf&) = delete;
-  HbmDeviceBuf& operator=(const HbmDeviceBuf&) = delete;
-  HbmDeviceBuf(HbmDeviceBuf&& o) noexcept : ptr(o.ptr) { o.ptr = nullptr; }
-  ~HbmDeviceBuf() {
-    if (ptr) (void)hipFree(ptr);
-  }
-  void alloc(size_t bytes) { HIP_CHECK(hipMalloc(&ptr, bytes)); }
-};
-
 struct HbmChunk {
-  HbmDeviceBuf buf;
+  DeviceBuf<uint64_t> buf;
   uint64_t first_word = 0;  // logical
   uint64_t words = 0;
 };
@@ -1948,15 +1245,10 @@ static void hbm_launch(int kind, const HbmLaunch& a) {
   const uint64_t nvec = a.nwords >> 1;
   const long want = (long)(nvec / (2 * (uint64_t)kHbmBlock)) + 1;
   const int grid = (int)std::min<long>(131072, std::max<long>(1024, want));
-  if (kind == kHbmFill)
-    hipLaunchKernelGGL(hbm_pattern_kernel<kHbmFill>, dim3(grid), dim3(kHbmBlock),
-                       0, 0, a);
-  else if (kind == kHbmVerifyInvert)
-    hipLaunchKernelGGL(hbm_pattern_kernel<kHbmVerifyInvert>, dim3(grid),
-                       dim3(kHbmBlock), 0, 0, a);
-  else
-    hipLaunchKernelGGL(hbm_pattern_kernel<kHbmVerify>, dim3(grid),
-                       dim3(kHbmBlock), 0, 0, a);
+  static void (*const kKernels[3])(HbmLaunch) = {  // indexed by kind
+      hbm_pattern_kernel<kHbmFill>, hbm_pattern_kernel<kHbmVerifyInvert>,
+      hbm_pattern_kernel<kHbmVerify>};
+  hipLaunchKernelGGL(kKernels[kind], dim3(grid), dim3(kHbmBlock), 0, 0, a);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2014,20 +1306,16 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
     HbmChunk& c = chunks.back();
     c.first_word = first_word + off;
     c.words = std::min(chunk_words, words - off);
-    c.buf.alloc((size_t)(c.words * 8));
+    c.buf = DeviceBuf<uint64_t>((size_t)c.words);
   }
 
-  HbmDeviceBuf d_ctl, d_shards, d_records;
-  const size_t shard_bytes = sizeof(uint64_t) * kHbmShards * kHbmShardStride;
-  d_ctl.alloc(sizeof(uint64_t) * kHbmCtlWords);
-  d_shards.alloc(shard_bytes);
-  d_records.alloc(sizeof(HbmRecord) * (size_t)max_records);
-  HIP_CHECK(hipMemset(d_ctl.ptr, 0, sizeof(uint64_t) * kHbmCtlWords));
-  HIP_CHECK(hipMemset(d_shards.ptr, 0, shard_bytes));
-  HIP_CHECK(hipMemset(d_records.ptr, 0, sizeof(HbmRecord) * (size_t)max_records));
-  CovEvent t0, t1;
-  t0.create();
-  t1.create();
+  DeviceBuf<unsigned long long> d_ctl(kHbmCtlWords);
+  DeviceBuf<unsigned long long> d_shards((size_t)kHbmShards * kHbmShardStride);
+  DeviceBuf<HbmRecord> d_records((size_t)max_records);
+  d_ctl.fill(0);
+  d_shards.fill(0);
+  d_records.fill(0);
+  EventTimer timer;
 
   static const char* const kKindNames[3] = {"fill", "verify_invert", "verify"};
   py::list phases;
@@ -2040,28 +1328,25 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
       const bool verifies = kind != kHbmFill;
       const bool poisoned = verifies && poison_word >= 0 &&
                             (poison_phase < 0 || poison_phase == verify_index);
-      HIP_CHECK(hipEventRecord(t0.ev));
-      for (const HbmChunk& c : chunks) {
-        HbmLaunch a;
-        a.buf = static_cast<uint64_t*>(c.buf.ptr);
-        a.nwords = c.words;
-        a.base = c.first_word;
-        a.seed = pseed;
-        a.poison_xor = poison_xor;
-        a.poison_stride = poison_stride;
-        a.poison_word = poisoned ? poison_word : -1;
-        a.ctl = static_cast<unsigned long long*>(d_ctl.ptr);
-        a.shards = static_cast<unsigned long long*>(d_shards.ptr);
-        a.records = static_cast<HbmRecord*>(d_records.ptr);
-        a.max_records = (uint32_t)max_records;
-        a.verify_index = (uint32_t)verify_index;
-        a.pattern = is_hash ? kHbmPatternHash : kHbmPatternChecker;
-        hbm_launch(kind, a);
-      }
-      HIP_CHECK(hipEventRecord(t1.ev));
-      HIP_CHECK(hipEventSynchronize(t1.ev));
-      float ms = 0.f;
-      HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+      const float ms = timer.time_ms([&] {
+        for (const HbmChunk& c : chunks) {
+          HbmLaunch a;
+          a.buf = c.buf.get();
+          a.nwords = c.words;
+          a.base = c.first_word;
+          a.seed = pseed;
+          a.poison_xor = poison_xor;
+          a.poison_stride = poison_stride;
+          a.poison_word = poisoned ? poison_word : -1;
+          a.ctl = d_ctl.get();
+          a.shards = d_shards.get();
+          a.records = d_records.get();
+          a.max_records = (uint32_t)max_records;
+          a.verify_index = (uint32_t)verify_index;
+          a.pattern = is_hash ? kHbmPatternHash : kHbmPatternChecker;
+          hbm_launch(kind, a);
+        }
+      });
       elapsed_ms += ms;
       // bytes the phase really moves: verify_invert reads and writes
       const double moved = (kind == kHbmVerifyInvert ? 2.0 : 1.0) * (double)nbytes;
@@ -2080,17 +1365,14 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
     }
   }
 
-  uint64_t ctl[kHbmCtlWords];
-  std::vector<uint64_t> shards((size_t)kHbmShards * kHbmShardStride);
-  HIP_CHECK(hipMemcpy(ctl, d_ctl.ptr, sizeof(ctl), hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(shards.data(), d_shards.ptr, shard_bytes,
-                      hipMemcpyDeviceToHost));
+  unsigned long long ctl[kHbmCtlWords];
+  std::vector<unsigned long long> shards(d_shards.size());
+  d_ctl.download(ctl, kHbmCtlWords);
+  d_shards.download(shards.data(), shards.size());
   const uint64_t claims = ctl[kHbmCtlClaims];
   const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)max_records);
   std::vector<HbmRecord> recs(kept);
-  if (kept)
-    HIP_CHECK(hipMemcpy(recs.data(), d_records.ptr, sizeof(HbmRecord) * kept,
-                        hipMemcpyDeviceToHost));
+  if (kept) d_records.download(recs.data(), kept);
   uint64_t words_verified = 0;
   for (int s = 0; s < kHbmShards; ++s)
     words_verified += shards[(size_t)s * kHbmShardStride];
@@ -2200,10 +1482,6 @@ constexpr int kXfXccs = 16;                // XCC_ID[3:0]
 constexpr int kXfMaxRecords = 4096;
 constexpr int kXfMaxBlocks = 1024;
 constexpr int kXfStaggerSleeps = 2;        // x s_sleep(127), 64 clocks each unit
-constexpr uint64_t kXfStaticKey = 0x5354415449435F58ull;
-constexpr uint64_t kXfAtomKey1 = 0x41544F4D31ull, kXfAtomKey2 = 0x41544F4D32ull,
-                   kXfAtomKey3 = 0x41544F4D33ull;
-constexpr int64_t kXfF32Bound = 1ll << 23;
 constexpr unsigned kXfPoisonPayload = 1u << 0, kXfPoisonHeader = 1u << 1,
                    kXfPoisonAdd32 = 1u << 2, kXfPoisonAdd64 = 1u << 3,
                    kXfPoisonAddF32 = 1u << 4, kXfPoisonMinMax = 1u << 5,
@@ -2243,21 +1521,6 @@ struct XfHandoff {
   uint32_t round, reps, group, G, slab_lines, max_records, poison_mask;
   int poison_pair;
 };
-
-__host__ __device__ inline uint64_t xf_static_word(uint64_t seed, uint64_t idx) {
-  return hbm_pattern_value(kHbmPatternHash, seed ^ kXfStaticKey, idx);
-}
-// round -1 is the initial upload
-__host__ __device__ inline uint64_t xf_payload_word(uint64_t seed, int64_t round,
-                                                    uint64_t idx) {
-  return hbm_pattern_value(kHbmPatternHash, seed + (uint64_t)round, idx);
-}
-__host__ __device__ inline uint64_t xf_line_index(uint32_t blocks,
-                                                  uint32_t slab_lines,
-                                                  uint32_t rep, uint32_t block,
-                                                  uint32_t line) {
-  return ((uint64_t)rep * blocks + block) * slab_lines + line;
-}
 
 // the rare path: claim a record slot, as hbm_report does
 __device__ __forceinline__ void xf_report(const XfHandoff& a, uint32_t rep,
@@ -2476,32 +1739,6 @@ struct alignas(128) XfCell {
 };
 static_assert(sizeof(XfCell) == 128, "one cell per 128-byte line");
 
-struct XfAtomVals {
-  uint64_t add64, mm;
-  uint32_t add32, x, o, a;
-  int addf;  // integer in [-8, 8], added as f32
-};
-
-// The one generator shared by the kernel and the host: what thread `id` adds
-// in repetition `rep`.  or/and operands are mostly neutral so the cells do
-// not saturate.
-__host__ __device__ inline XfAtomVals xf_atom_vals(uint64_t seed, uint64_t id,
-                                                   uint32_t rep) {
-  const uint64_t n = id * 64 + rep;
-  const uint64_t h1 = hbm_pattern_value(kHbmPatternHash, seed ^ kXfAtomKey1, n);
-  const uint64_t h2 = hbm_pattern_value(kHbmPatternHash, seed ^ kXfAtomKey2, n);
-  const uint64_t h3 = hbm_pattern_value(kHbmPatternHash, seed ^ kXfAtomKey3, n);
-  XfAtomVals v;
-  v.add32 = (uint32_t)h1;
-  v.addf = (int)((h1 >> 32) % 17) - 8;
-  v.add64 = h2;
-  v.mm = h3;
-  v.x = (uint32_t)(h1 >> 20);
-  v.o = ((h2 >> 40) & 1023) == 0 ? 1u << ((h2 >> 8) & 31) : 0u;
-  v.a = ((h2 >> 50) & 1023) == 0 ? ~(1u << ((h2 >> 16) & 31)) : ~0u;
-  return v;
-}
-
 constexpr int kXfActlTicketRange = 0, kXfActlWords = 2;
 
 struct XfAtomics {
@@ -2548,49 +1785,6 @@ __global__ void __launch_bounds__(kXfBlock) xcd_atomics_kernel(XfAtomics a) {
     atomicAdd(&a.adders[__builtin_amdgcn_s_getreg(kCovHwRegXccId) & (kXfXccs - 1)],
               1u);
 #endif
-}
-
-// Expected cell contents after `threads` threads ran `reps` repetitions.
-struct XfAtomExpected {
-  std::vector<uint32_t> add32, x, o, a;
-  std::vector<uint64_t> add64, max64, min64;
-  std::vector<int64_t> addf;
-};
-
-static XfAtomExpected xf_atom_expected(uint64_t seed, uint64_t threads, int reps,
-                                       int cells) {
-  XfAtomExpected e;
-  e.add32.assign(cells, 0u);
-  e.x.assign(cells, 0u);
-  e.o.assign(cells, 0u);
-  e.a.assign(cells, ~0u);
-  e.add64.assign(cells, 0ull);
-  e.max64.assign(cells, 0ull);
-  e.min64.assign(cells, ~0ull);
-  e.addf.assign(cells, 0);
-  std::vector<int64_t> mag(cells, 0);
-  for (uint64_t id = 0; id < threads; ++id)
-    for (int rep = 0; rep < reps; ++rep) {
-      const size_t c = (size_t)((id + (uint64_t)rep) % (uint64_t)cells);
-      const XfAtomVals v = xf_atom_vals(seed, id, (uint32_t)rep);
-      e.add32[c] += v.add32;
-      e.add64[c] += v.add64;
-      e.addf[c] += v.addf;
-      mag[c] += v.addf < 0 ? -v.addf : v.addf;
-      e.max64[c] = std::max(e.max64[c], v.mm);
-      e.min64[c] = std::min(e.min64[c], v.mm);
-      e.x[c] ^= v.x;
-      e.o[c] |= v.o;
-      e.a[c] &= v.a;
-    }
-  // enforced, not assumed: below 2^23 every partial sum is an exact f32
-  for (int c = 0; c < cells; ++c)
-    if (mag[c] > kXfF32Bound)
-      throw std::invalid_argument(
-          "xcd_fabric: the f32 operands of cell " + std::to_string(c) +
-          " sum to a magnitude of " + std::to_string(mag[c]) +
-          " > 2^23; use more cells or fewer reps");
-  return e;
 }
 
 struct XfShape {
@@ -2677,12 +1871,6 @@ static py::dict xcd_fabric_reference(int blocks, uint64_t seed, int reps,
   return out;
 }
 
-static uint32_t xf_f32_bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, sizeof(u));
-  return u;
-}
-
 static void xf_mismatch(py::list& out, const char* comparison, const char* op,
                         int cell, py::object expected, py::object got) {
   py::dict e;
@@ -2707,53 +1895,41 @@ static py::dict xf_run_atomics(int cus, const XfShape& s, uint64_t seed,
     c.min64 = ~0ull;
     c.a = ~0u;
   }
-  HbmDeviceBuf d_cells, d_ticket, d_seen, d_adders, d_ctl;
-  d_cells.alloc(sizeof(XfCell) * cells.size());
-  d_ticket.alloc(128);
-  d_seen.alloc(sizeof(uint32_t) * total);
-  d_adders.alloc(sizeof(uint32_t) * kXfXccs);
-  d_ctl.alloc(sizeof(uint64_t) * kXfActlWords);
-  HIP_CHECK(hipMemcpy(d_cells.ptr, cells.data(), sizeof(XfCell) * cells.size(),
-                      hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemset(d_ticket.ptr, 0, 128));
-  HIP_CHECK(hipMemset(d_seen.ptr, 0, sizeof(uint32_t) * total));
-  HIP_CHECK(hipMemset(d_adders.ptr, 0, sizeof(uint32_t) * kXfXccs));
-  HIP_CHECK(hipMemset(d_ctl.ptr, 0, sizeof(uint64_t) * kXfActlWords));
-  CovEvent t0, t1;
-  t0.create();
-  t1.create();
+  DeviceBuf<XfCell> d_cells(cells.size());
+  DeviceBuf<uint32_t> d_ticket(kXfTicketStride);  // a 128-byte line of its own
+  DeviceBuf<uint32_t> d_seen(total), d_adders(kXfXccs);
+  DeviceBuf<unsigned long long> d_ctl(kXfActlWords);
+  d_cells.upload(cells.data(), cells.size());
+  d_ticket.fill(0);
+  d_seen.fill(0);
+  d_adders.fill(0);
+  d_ctl.fill(0);
+  EventTimer timer;
 
   XfAtomics a;
-  a.cells = static_cast<XfCell*>(d_cells.ptr);
-  a.ticket = static_cast<uint32_t*>(d_ticket.ptr);
-  a.seen = static_cast<uint32_t*>(d_seen.ptr);
-  a.adders = static_cast<uint32_t*>(d_adders.ptr);
-  a.ctl = static_cast<unsigned long long*>(d_ctl.ptr);
+  a.cells = d_cells.get();
+  a.ticket = d_ticket.get();
+  a.seen = d_seen.get();
+  a.adders = d_adders.get();
+  a.ctl = d_ctl.get();
   a.seed = seed;
   a.reps = (uint32_t)s.reps;
   a.ncells = (uint32_t)s.cells;
   a.total = total;
-  HIP_CHECK(hipEventRecord(t0.ev));
-  hipLaunchKernelGGL(xcd_atomics_kernel, dim3(grid), dim3(kXfBlock), 0, 0, a);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(t1.ev));
-  HIP_CHECK(hipEventSynchronize(t1.ev));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+  const float ms = timer.time_ms([&] {
+    hipLaunchKernelGGL(xcd_atomics_kernel, dim3(grid), dim3(kXfBlock), 0, 0, a);
+    HIP_CHECK(hipGetLastError());
+  });
   elapsed_ms += ms;
 
   std::vector<uint32_t> seen(total), adders(kXfXccs);
   uint32_t counter = 0;
-  uint64_t ctl[kXfActlWords];
-  HIP_CHECK(hipMemcpy(cells.data(), d_cells.ptr, sizeof(XfCell) * cells.size(),
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(seen.data(), d_seen.ptr, sizeof(uint32_t) * total,
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(adders.data(), d_adders.ptr, sizeof(uint32_t) * kXfXccs,
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(&counter, d_ticket.ptr, sizeof(counter),
-                      hipMemcpyDeviceToHost));
-  HIP_CHECK(hipMemcpy(ctl, d_ctl.ptr, sizeof(ctl), hipMemcpyDeviceToHost));
+  unsigned long long ctl[kXfActlWords];
+  d_cells.download(cells.data(), cells.size());
+  d_seen.download(seen.data(), seen.size());
+  d_adders.download(adders.data(), adders.size());
+  d_ticket.download(&counter, 1);
+  d_ctl.download(ctl, kXfActlWords);
 
   // test hook: data only, bit 0 of the expected value
   const auto px = [&](unsigned bit) { return (s.poison_mask & bit) ? 1u : 0u; };
@@ -2779,8 +1955,8 @@ static py::dict xf_run_atomics(int cus, const XfShape& s, uint64_t seed,
     const uint64_t w64 = e.add64[c] ^ (uint64_t)px(kXfPoisonAdd64);
     if (k.add64 != w64)
       xf_mismatch(mism, "add_u64", "add_u64", c, py::int_(w64), py::int_(k.add64));
-    const uint32_t wf = xf_f32_bits((float)e.addf[c]) ^ px(kXfPoisonAddF32);
-    if (xf_f32_bits(k.addf) != wf) {
+    const uint32_t wf = f32_bits((float)e.addf[c]) ^ px(kXfPoisonAddF32);
+    if (f32_bits(k.addf) != wf) {
       float want;
       std::memcpy(&want, &wf, sizeof(want));
       xf_mismatch(mism, "add_f32", "add_f32", c, py::float_((double)want),
@@ -2864,10 +2040,8 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
   const size_t lines = (size_t)reps * nblocks * (size_t)slab_lines;
   const size_t slab_words = lines * kXfLineWords;
   const size_t n_tickets = (size_t)reps * (size_t)G;
-  const size_t ticket_bytes = n_tickets * kXfTicketStride * sizeof(uint32_t);
   const size_t writer_count = (size_t)reps * nblocks;
   constexpr size_t kPlane = (size_t)kXfXccs * kXfXccs;
-  const size_t pair_bytes = sizeof(uint64_t) * kXfPairPlanes * kPlane;
 
   // the initial upload plays round -1
   std::vector<uint64_t> h_slab(slab_words);
@@ -2876,26 +2050,21 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
                     ? xf_static_word(seed, i)
                     : xf_payload_word(seed, -1, i);
 
-  HbmDeviceBuf d_slab, d_tickets, d_writer, d_ctl, d_pair, d_records;
-  d_slab.alloc(slab_words * sizeof(uint64_t));
-  d_tickets.alloc(ticket_bytes);
-  d_writer.alloc(writer_count * sizeof(uint32_t));
-  d_ctl.alloc(sizeof(uint64_t) * kXfCtlWords);
-  d_pair.alloc(pair_bytes);
-  d_records.alloc(sizeof(XfRecord) * (size_t)max_records);
-  HIP_CHECK(hipMemcpy(d_slab.ptr, h_slab.data(), slab_words * sizeof(uint64_t),
-                      hipMemcpyHostToDevice));
-  HIP_CHECK(hipMemset(d_writer.ptr, 0xFF, writer_count * sizeof(uint32_t)));
-  HIP_CHECK(hipMemset(d_ctl.ptr, 0, sizeof(uint64_t) * kXfCtlWords));
-  HIP_CHECK(hipMemset(d_pair.ptr, 0, pair_bytes));
-  HIP_CHECK(hipMemset(d_records.ptr, 0, sizeof(XfRecord) * (size_t)max_records));
-  CovEvent t0, t1;
-  t0.create();
-  t1.create();
+  DeviceBuf<uint64_t> d_slab(slab_words);
+  DeviceBuf<uint32_t> d_tickets(n_tickets * kXfTicketStride);
+  DeviceBuf<uint32_t> d_writer(writer_count);
+  DeviceBuf<unsigned long long> d_ctl(kXfCtlWords), d_pair(kXfPairPlanes * kPlane);
+  DeviceBuf<XfRecord> d_records((size_t)max_records);
+  d_slab.upload(h_slab.data(), slab_words);
+  d_writer.fill(0xFF);
+  d_ctl.fill(0);
+  d_pair.fill(0);
+  d_records.fill(0);
+  EventTimer timer;
 
-  std::vector<uint32_t> h_tickets(n_tickets * kXfTicketStride);
+  std::vector<uint32_t> h_tickets(d_tickets.size());
   std::vector<uint32_t> h_writer(writer_count);
-  std::vector<uint64_t> h_pair(kXfPairPlanes * kPlane);
+  std::vector<unsigned long long> h_pair(d_pair.size());
   std::vector<uint64_t> writes_per_xcc(kXfXccs, 0);
   uint64_t ticket_counter_errors = 0, writer_host_range = 0;
   int rounds = 0, pairs_covered = 0, xcc_seen = 0;
@@ -2904,12 +2073,12 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
   py::list round_ms;
   while (rounds < max_rounds) {
     XfHandoff a;
-    a.slab = static_cast<uint64_t*>(d_slab.ptr);
-    a.tickets = static_cast<uint32_t*>(d_tickets.ptr);
-    a.writer_xcc = static_cast<uint32_t*>(d_writer.ptr);
-    a.ctl = static_cast<unsigned long long*>(d_ctl.ptr);
-    a.pair = static_cast<unsigned long long*>(d_pair.ptr);
-    a.records = static_cast<XfRecord*>(d_records.ptr);
+    a.slab = d_slab.get();
+    a.tickets = d_tickets.get();
+    a.writer_xcc = d_writer.get();
+    a.ctl = d_ctl.get();
+    a.pair = d_pair.get();
+    a.records = d_records.get();
     a.seed = seed;
     a.round = (uint32_t)rounds;
     a.reps = (uint32_t)reps;
@@ -2919,25 +2088,19 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
     a.max_records = (uint32_t)max_records;
     a.poison_mask = poison_mask;
     a.poison_pair = poison_pair;
-    HIP_CHECK(hipEventRecord(t0.ev));
-    // the ticket counters are zeroed on the launch stream ahead of every launch
-    HIP_CHECK(hipMemsetAsync(d_tickets.ptr, 0, ticket_bytes, 0));
-    hipLaunchKernelGGL(xcd_handoff_kernel, dim3(nblocks), dim3(kXfBlock), 0, 0, a);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(t1.ev));
-    HIP_CHECK(hipEventSynchronize(t1.ev));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+    const float ms = timer.time_ms([&] {
+      // the ticket counters are zeroed on the launch stream ahead of every launch
+      d_tickets.fill_async(0);
+      hipLaunchKernelGGL(xcd_handoff_kernel, dim3(nblocks), dim3(kXfBlock), 0, 0, a);
+      HIP_CHECK(hipGetLastError());
+    });
     elapsed_ms += ms;
     round_ms.append((double)ms);
     ++rounds;
 
-    HIP_CHECK(hipMemcpy(h_tickets.data(), d_tickets.ptr, ticket_bytes,
-                        hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(h_writer.data(), d_writer.ptr,
-                        writer_count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_CHECK(hipMemcpy(h_pair.data(), d_pair.ptr, pair_bytes,
-                        hipMemcpyDeviceToHost));
+    d_tickets.download(h_tickets.data(), h_tickets.size());
+    d_writer.download(h_writer.data(), h_writer.size());
+    d_pair.download(h_pair.data(), h_pair.size());
     for (size_t t = 0; t < n_tickets; ++t)
       ticket_counter_errors += h_tickets[t * kXfTicketStride] != (uint32_t)group;
     for (uint32_t wx : h_writer) {
@@ -2960,14 +2123,12 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
     if (rounds >= 2 && pairs_covered >= xcc_seen * xcc_seen) break;
   }
 
-  uint64_t ctl[kXfCtlWords];
-  HIP_CHECK(hipMemcpy(ctl, d_ctl.ptr, sizeof(ctl), hipMemcpyDeviceToHost));
+  unsigned long long ctl[kXfCtlWords];
+  d_ctl.download(ctl, kXfCtlWords);
   const uint64_t claims = ctl[kXfCtlClaims];
   const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)max_records);
   std::vector<XfRecord> recs(kept);
-  if (kept)
-    HIP_CHECK(hipMemcpy(recs.data(), d_records.ptr, sizeof(XfRecord) * kept,
-                        hipMemcpyDeviceToHost));
+  if (kept) d_records.download(recs.data(), kept);
 
   py::dict atomics = xf_run_atomics(cus, s, seed, elapsed_ms);
 
