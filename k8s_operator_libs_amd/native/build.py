@@ -17,6 +17,7 @@ SOURCES = (
     SOURCE,
     os.path.join(PKG_DIR, "hip_util.hpp"),
     os.path.join(PKG_DIR, "validator_problems.hpp"),
+    os.path.join(PKG_DIR, "lds_problems.hpp"),
 )
 OUTPUT = os.path.join(PKG_DIR, "_gpu_validator.so")
 JSONOPS_SOURCE = os.path.join(PKG_DIR, "jsonops.cpp")

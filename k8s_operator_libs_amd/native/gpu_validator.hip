@@ -31,6 +31,12 @@
 //                           (agent-scope release, ticket, acquire) and every
 //                           device-scope atomic, exact, attributed per
 //                           (writer, reader) XCC pair (opt-in)
+//   lds_integrity_check() — all 160 KiB of LDS on every CU: moving inversions
+//                           in b32 / b64 / b128, byte and 16-bit stores,
+//                           ds_read_b64_tr_b16, direct global->LDS loads, LDS
+//                           atomics and ds_bpermute / ds_permute, exact,
+//                           attributed per CU and word (opt-in)
+//   lds_tr_tile()         — one ds_read_b64_tr_b16, raw elements returned
 //
 // This file holds the kernels, the HIP host drivers, the py::dict conversion
 // and the module table.  Device memory and events are owned by the holders in
@@ -2222,8 +2228,795 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// LDS data-integrity check.  One 256-thread workgroup claims all 160 KiB of a
+// CU's Local Data Share as one static array, so exactly one workgroup fits on
+// a CU, and runs `reps` repetitions of six phases over it (generators and the
+// layouts in lds_problems.hpp):
+//   bit 0 pattern    moving inversions over all 40960 words: `passes` hash
+//                    patterns and one checker, each as fill p / verify p and
+//                    write ~p / verify ~p, the three steps in three different
+//                    widths out of b32, b64, b128, rotated per pattern
+//   bit 1 subword    every word assembled over its inverse from four byte
+//                    stores or two 16-bit stores issued by different waves,
+//                    verified as b32 and read back as u8 / u16
+//   bit 2 transpose  the whole array read with ds_read_b64_tr_b16 as 4 x 16
+//                    blocks, under 64-byte and under 160-byte rows
+//   bit 3 dma        the whole array filled by direct global->LDS loads, half
+//                    16 bytes and half 4 bytes per lane, from permuted source
+//                    addresses; verified with ordinary reads
+//   bit 4 atomics    the LDS ALU: u32 / u64 / f32 add, u32 max / min, xor, or,
+//                    and, one compare-and-swap claim per cell
+//   bit 5 permute    ds_bpermute_b32 / ds_permute_b32 with lane permutations
+//                    that change every step
+//
+// A step splits the array into 160 chunks of 1 KiB; chunk c of step s belongs
+// to wave (c + s) % 4 and s advances with every step, so a word is always
+// verified by another wave than the one that wrote it.  Workgroup barriers
+// separate the steps.  The whole array is in use, so nothing is reduced
+// through LDS: fail masks go through ballots, counts through lane shuffles,
+// and both through global atomics once per wave at the end.
+//
+// Grid, placement key, bounded relaunch and the fixed amount of work per
+// workgroup are those of cu_coverage_kernel; coverage is per CU, LDS belongs
+// to the CU.  The poison hook is data only: it XORs into the *expected*
+// values and never alters LDS, so a record's `got` is real LDS content.
+// ---------------------------------------------------------------------------
+
+constexpr int kLdsCtlErrors = 0, kLdsCtlXor = 1, kLdsCtlClaims = 2,
+              kLdsCtlWords = 4;
+constexpr int kLdsKeyPlanes = 4;  // workgroups | fail | hw_id | xcc_id
+
+struct LdsRecord {
+  uint32_t key, block, rep, phase, detail, word;
+  uint64_t expected, got;
+};
+
+struct LdsLaunch {
+  const uint32_t* src;           // kLdsWords words, the source of the dma phase
+  uint32_t* keys;                // [kLdsKeyPlanes][kCovKeys]
+  unsigned long long* ctl;
+  unsigned long long* counters;  // [kLdsPhases] items compared
+  LdsRecord* records;
+  uint64_t seed;
+  uint32_t reps, passes, max_records, poison_mask, poison_xor;
+  int poison_key, poison_all, poison_word;
+};
+
+struct LdsLane {
+  uint32_t key, block, rep, pm;
+  int tid, lane, wave;
+  uint32_t fail, bad;
+  uint64_t bad_xor;
+  uint32_t compared[kLdsPhases];
+};
+
+using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+using s16x4 = __attribute__((ext_vector_type(4))) short;
+
+#if defined(__gfx950__)
+// the rare path: count the mismatch and, while slots are left, claim a record
+// (by value and out of line: the lane's counters stay in registers)
+__device__ __noinline__ void lds_record(unsigned long long* ctl, LdsRecord* records,
+                                        uint32_t max_records, LdsRecord r) {
+  if (__hip_atomic_load(&ctl[kLdsCtlClaims], __ATOMIC_RELAXED,
+                        __HIP_MEMORY_SCOPE_AGENT) >= max_records)
+    return;
+  const unsigned long long slot = atomicAdd(&ctl[kLdsCtlClaims], 1ull);
+  if (slot < max_records) records[slot] = r;  // claims past the cap are dropped
+}
+
+__device__ __forceinline__ void lds_check(const LdsLaunch& a, LdsLane& st,
+                                          int phase, uint32_t detail,
+                                          uint32_t word, uint64_t expected,
+                                          uint64_t got) {
+  ++st.compared[phase];
+  if (expected != got) {
+    ++st.bad;
+    st.bad_xor |= expected ^ got;
+    st.fail |= 1u << phase;
+    const LdsRecord r = {st.key, st.block, st.rep, (uint32_t)phase, detail, word,
+                         expected, got};
+    lds_record(a.ctl, a.records, a.max_records, r);
+  }
+}
+
+// first word of the j-th chunk (j < 40) of this wave in step s
+__device__ __forceinline__ uint32_t lds_chunk(const LdsLane& st, uint32_t s, int j) {
+  return ((((uint32_t)st.wave - s) & 3u) + 4u * (uint32_t)j) * kLdsChunkWords;
+}
+
+// One step of a moving-inversions pattern in W-word accesses.  KIND 0 fills
+// with p, 1 verifies p and writes ~p, 2 verifies ~p.
+template <int W, int KIND>
+__device__ __forceinline__ void lds_pattern_step(uint32_t* lds, const LdsLaunch& a,
+                                                 LdsLane& st, int pat, uint32_t s) {
+  const uint32_t inv = KIND == 2 ? ~0u : 0u, winv = KIND == 1 ? ~0u : 0u;
+  const bool poisoned = (st.pm >> kLdsPhasePattern) & 1u;
+#pragma unroll 1
+  for (int j = 0; j < kLdsChunks / 4; ++j) {
+    const uint32_t c0 = lds_chunk(st, s, j);
+#pragma unroll
+    for (int it = 0; it < 4 / W; ++it) {
+      const uint32_t w0 = c0 + (uint32_t)(it * 64 + st.lane) * W;
+      uint32_t g[W], p[W];
+      for (int k = 0; k < W; ++k)
+        p[k] = lds_pattern_word(a.seed, (int)a.passes, st.block, st.rep, pat, w0 + k);
+      if (KIND != 0) {
+        if constexpr (W == 1) {
+          g[0] = lds[w0];
+        } else if constexpr (W == 2) {
+          const u32x2 v = *reinterpret_cast<const u32x2*>(lds + w0);
+          g[0] = v[0];
+          g[1] = v[1];
+        } else {
+          const u32x4 v = *reinterpret_cast<const u32x4*>(lds + w0);
+          for (int k = 0; k < 4; ++k) g[k] = v[k];
+        }
+        for (int k = 0; k < W; ++k) {
+          uint32_t want = p[k] ^ inv;
+          // test hook: data only, moves the *expected* word
+          if (poisoned && (a.poison_word < 0 || (uint32_t)a.poison_word == w0 + k))
+            want ^= a.poison_xor;
+          lds_check(a, st, kLdsPhasePattern, (uint32_t)(pat * 4 + KIND), w0 + k,
+                    want, g[k]);
+        }
+      }
+      if (KIND != 2) {
+        if constexpr (W == 1) {
+          lds[w0] = p[0] ^ winv;
+        } else if constexpr (W == 2) {
+          u32x2 v;
+          v[0] = p[0] ^ winv;
+          v[1] = p[1] ^ winv;
+          *reinterpret_cast<u32x2*>(lds + w0) = v;
+        } else {
+          u32x4 v;
+          for (int k = 0; k < 4; ++k) v[k] = p[k] ^ winv;
+          *reinterpret_cast<u32x4*>(lds + w0) = v;
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
+template <int KIND>
+__device__ __forceinline__ void lds_pattern_dispatch(uint32_t* lds,
+                                                     const LdsLaunch& a,
+                                                     LdsLane& st, int pat,
+                                                     uint32_t s) {
+  switch (lds_pattern_width(pat, KIND)) {  // uniform
+    case 0: lds_pattern_step<1, KIND>(lds, a, st, pat, s); break;
+    case 1: lds_pattern_step<2, KIND>(lds, a, st, pat, s); break;
+    default: lds_pattern_step<4, KIND>(lds, a, st, pat, s); break;
+  }
+}
+
+__device__ __forceinline__ void lds_phase_subword(uint32_t* lds, const LdsLaunch& a,
+                                                  LdsLane& st, uint32_t& s) {
+  const uint32_t px = (st.pm >> kLdsPhaseSubword) & 1u;
+  // explicitly LDS pointers: a volatile access through a generic pointer
+  // would be a flat instruction
+  typedef volatile __attribute__((address_space(3))) uint8_t* lds_b8_t;
+  typedef volatile __attribute__((address_space(3))) uint16_t* lds_b16_t;
+  const lds_b8_t b8 = (lds_b8_t)lds;
+  const lds_b16_t b16 = (lds_b16_t)lds;
+  // the background: the inverse of every word
+#pragma unroll 1
+  for (int j = 0; j < kLdsChunks / 4; ++j)
+    for (int it = 0; it < 4; ++it) {
+      const uint32_t w = lds_chunk(st, s, j) + (uint32_t)(it * 64 + st.lane);
+      lds[w] = ~lds_subword_word(a.seed, st.block, st.rep, w);
+    }
+  ++s;
+  __syncthreads();
+  // every wave stores into every chunk: byte k of the words of an even chunk,
+  // half k & 1 of words 128 (k >> 1) .. + 127 of an odd one, k its role there
+#pragma unroll 1
+  for (uint32_t c = 0; c < (uint32_t)kLdsChunks; ++c) {
+    const uint32_t k = ((uint32_t)st.wave + c + s) & 3u;
+    if ((c & 1u) == 0) {
+      for (int it = 0; it < 4; ++it) {
+        const uint32_t w = c * kLdsChunkWords + (uint32_t)(it * 64 + st.lane);
+        const uint32_t v = lds_subword_word(a.seed, st.block, st.rep, w);
+        b8[4 * w + k] = (uint8_t)(v >> (8 * k));
+      }
+    } else {
+      for (int it = 0; it < 2; ++it) {
+        const uint32_t w = c * kLdsChunkWords + (k >> 1) * 128u +
+                           (uint32_t)(it * 64 + st.lane);
+        const uint32_t v = lds_subword_word(a.seed, st.block, st.rep, w);
+        b16[2 * w + (k & 1u)] = (uint16_t)(v >> (16 * (k & 1u)));
+      }
+    }
+  }
+  ++s;
+  __syncthreads();
+  // whole words
+#pragma unroll 1
+  for (int j = 0; j < kLdsChunks / 4; ++j)
+    for (int it = 0; it < 4; ++it) {
+      const uint32_t w = lds_chunk(st, s, j) + (uint32_t)(it * 64 + st.lane);
+      const uint32_t want = lds_subword_word(a.seed, st.block, st.rep, w) ^ px;
+      lds_check(a, st, kLdsPhaseSubword, 0u, w, want, lds[w]);
+    }
+  // and bytes and halves, each read by another wave than the one that stored it
+#pragma unroll 1
+  for (uint32_t c = 0; c < (uint32_t)kLdsChunks; ++c) {
+    const uint32_t k = ((uint32_t)st.wave + c + s + 1u) & 3u;
+    if ((c & 1u) == 0) {
+      for (int it = 0; it < 4; ++it) {
+        const uint32_t w = c * kLdsChunkWords + (uint32_t)(it * 64 + st.lane);
+        const uint32_t v = lds_subword_word(a.seed, st.block, st.rep, w) ^ px;
+        lds_check(a, st, kLdsPhaseSubword, 1u + k, w, (v >> (8 * k)) & 0xFFu,
+                  b8[4 * w + k]);
+      }
+    } else {
+      for (int it = 0; it < 2; ++it) {
+        const uint32_t w = c * kLdsChunkWords + (k >> 1) * 128u +
+                           (uint32_t)(it * 64 + st.lane);
+        const uint32_t v = lds_subword_word(a.seed, st.block, st.rep, w) ^ px;
+        lds_check(a, st, kLdsPhaseSubword, 5u + (k & 1u), w,
+                  (v >> (16 * (k & 1u))) & 0xFFFFu, b16[2 * w + (k & 1u)]);
+      }
+    }
+  }
+  ++s;
+  __syncthreads();
+}
+
+__device__ __forceinline__ void lds_phase_transpose(uint32_t* lds,
+                                                    const LdsLaunch& a, LdsLane& st,
+                                                    uint32_t& s) {
+  const uint32_t px = (st.pm >> kLdsPhaseTranspose) & 1u;
+#pragma unroll 1
+  for (int j = 0; j < kLdsChunks / 4; ++j) {
+    const uint32_t w0 = lds_chunk(st, s, j) + (uint32_t)st.lane * 4u;
+    u32x4 v;
+    for (int k = 0; k < 4; ++k)
+      v[k] = lds_tr_word(a.seed, st.block, st.rep, w0 + k);
+    *reinterpret_cast<u32x4*>(lds + w0) = v;
+  }
+  ++s;
+  __syncthreads();
+  // One wave-instruction reads four blocks, one per 16-lane group.  The loops
+  // are uniform and every lane holds an in-bounds 8-byte-aligned address, so
+  // EXEC is all ones at the read; the compare comes afterwards.
+  const uint32_t i = (uint32_t)st.lane & 15u, grp = (uint32_t)st.lane >> 4;
+  for (int layout = 0; layout < 2; ++layout) {
+    const int R = layout == 0 ? kLdsTrRowBlocks[0] : kLdsTrRowBlocks[1];
+#pragma unroll 1
+    for (int j = 0; j < kLdsTrBlocks / 16; ++j) {
+      const uint32_t n = (((uint32_t)st.wave - s) & 3u) + 4u * (uint32_t)j;
+      const uint32_t b = 4u * n + grp;
+      const uint32_t off = lds_tr_lane_offset(R, b, i);
+      const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) s16x4*)(
+              reinterpret_cast<char*>(lds) + off));
+      for (uint32_t q = 0; q < 4; ++q) {
+        const uint32_t e = lds_tr_expected_elem(R, b, i, q);
+        lds_check(a, st, kLdsPhaseTranspose, (uint32_t)layout, e >> 1,
+                  lds_tr_elem(a.seed, st.block, st.rep, e) ^ px,
+                  (uint32_t)(uint16_t)r[q]);
+      }
+    }
+    ++s;
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ void lds_phase_dma(uint32_t* lds, const LdsLaunch& a,
+                                              LdsLane& st, uint32_t& s) {
+  const uint32_t px = (st.pm >> kLdsPhaseDma) & 1u;
+  typedef __attribute__((address_space(1))) const void* gptr_t;
+  typedef __attribute__((address_space(3))) void* lptr_t;
+#pragma unroll 1
+  for (int j = 0; j < kLdsChunks / 4; ++j) {
+    const uint32_t c0 = lds_chunk(st, s, j);  // wave-uniform: the LDS base
+    if (lds_dma_wide(st.rep, c0 / kLdsChunkWords)) {
+      // lane l lands at words 4l .. 4l+3 of the chunk
+      const uint32_t src =
+          lds_dma_src_index(st.block, st.rep, c0 + 4u * (uint32_t)st.lane);
+      __builtin_amdgcn_global_load_lds((gptr_t)(a.src + src), (lptr_t)(lds + c0),
+                                       16, 0, 0);
+    } else {
+      for (uint32_t q = 0; q < 4; ++q) {  // load q, lane l lands at word 64q + l
+        const uint32_t src = lds_dma_src_index(
+            st.block, st.rep, c0 + 64u * q + (uint32_t)st.lane);
+        __builtin_amdgcn_global_load_lds((gptr_t)(a.src + src),
+                                         (lptr_t)(lds + c0 + 64u * q), 4, 0, 0);
+      }
+    }
+  }
+  ++s;
+  // a direct load is a pending LDS write on the vector-memory counter
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+#pragma unroll 1
+  for (int j = 0; j < kLdsChunks / 4; ++j) {
+    const uint32_t w0 = lds_chunk(st, s, j) + (uint32_t)st.lane * 4u;
+    const u32x4 g = *reinterpret_cast<const u32x4*>(lds + w0);
+    for (int k = 0; k < 4; ++k) {
+      // volatile: the source is re-read from global memory, never folded
+      const uint32_t want = ((const volatile __attribute__((address_space(1)))
+                                  uint32_t*)a.src)[lds_dma_src_index(
+          st.block, st.rep, w0 + k)];
+      lds_check(a, st, kLdsPhaseDma, 0u, w0 + k, want ^ px, g[k]);
+    }
+  }
+  ++s;
+  __syncthreads();
+}
+
+__device__ __forceinline__ void lds_phase_atomics(uint32_t* lds, const LdsLaunch& a,
+                                                  LdsLane& st) {
+  const uint32_t px = (st.pm >> kLdsPhaseAtomics) & 1u;
+  const uint32_t tid = (uint32_t)st.tid;
+  if (tid < (uint32_t)kLdsAtomCells) {
+    const uint32_t base = lds_atom_cell_base(tid);
+    for (int f = 0; f <= kLdsCellConfirm; ++f) lds[base + f] = 0u;
+    lds[base + kLdsCellMin] = ~0u;
+    lds[base + kLdsCellAnd] = ~0u;
+  }
+  __syncthreads();
+  for (uint32_t step = 0; step < (uint32_t)kLdsAtomSteps; ++step) {
+    uint32_t* c = lds + lds_atom_cell_base((tid + step) % kLdsAtomCells);
+    const LdsAtomVals v = lds_atom_vals(a.seed, st.block, st.rep, tid, step);
+    __hip_atomic_fetch_add(c + kLdsCellAdd32, v.add32, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(c + kLdsCellAdd64),
+                           (unsigned long long)v.add64, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(reinterpret_cast<float*>(c + kLdsCellAddF),
+                           (float)v.addf, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_max(c + kLdsCellMax, v.mm, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_min(c + kLdsCellMin, v.mm, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_xor(c + kLdsCellXor, v.x, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_or(c + kLdsCellOr, v.o, __ATOMIC_RELAXED,
+                          __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_and(c + kLdsCellAnd, v.a, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  {  // single-shot compare-and-swap: one attempt, the winner confirms
+    uint32_t* c = lds + lds_atom_cell_base(tid % kLdsAtomCells);
+    if (atomicCAS(c + kLdsCellClaim, 0u, tid + 1u) == 0u)
+      c[kLdsCellConfirm] = tid + 1u;
+  }
+  __syncthreads();
+  // every wave compares a part of every cell, lane l cell l
+  const uint32_t cell = (uint32_t)st.lane;
+  const uint32_t base = lds_atom_cell_base(cell);
+  const LdsAtomCell e = lds_atom_expected_cell(a.seed, st.block, st.rep, cell);
+  if (st.wave == 0) {
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellAdd32, base + kLdsCellAdd32,
+              e.add32 ^ px, lds[base + kLdsCellAdd32]);
+    const uint64_t got64 = (uint64_t)lds[base + kLdsCellAdd64] |
+                           (uint64_t)lds[base + kLdsCellAdd64 + 1] << 32;
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellAdd64, base + kLdsCellAdd64,
+              e.add64 ^ px, got64);
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellAddF, base + kLdsCellAddF,
+              __float_as_uint((float)e.addf) ^ px, lds[base + kLdsCellAddF]);
+  } else if (st.wave == 1) {
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellMax, base + kLdsCellMax,
+              e.max32 ^ px, lds[base + kLdsCellMax]);
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellMin, base + kLdsCellMin,
+              e.min32 ^ px, lds[base + kLdsCellMin]);
+  } else if (st.wave == 2) {
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellXor, base + kLdsCellXor, e.x ^ px,
+              lds[base + kLdsCellXor]);
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellOr, base + kLdsCellOr, e.o ^ px,
+              lds[base + kLdsCellOr]);
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellAnd, base + kLdsCellAnd, e.a ^ px,
+              lds[base + kLdsCellAnd]);
+  } else {
+    // the winner of cell c is some thread t with t % 64 == c; expected is the
+    // cell number where the claim is none
+    const uint32_t claim = lds[base + kLdsCellClaim];
+    const bool valid = claim >= 1u && claim <= (uint32_t)kLdsBlock &&
+                       (claim - 1u) % kLdsAtomCells == cell;
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellClaim, base + kLdsCellClaim,
+              (valid ? claim : cell + 1u) ^ px, claim);
+    lds_check(a, st, kLdsPhaseAtomics, kLdsCellConfirm, base + kLdsCellConfirm,
+              claim ^ px, lds[base + kLdsCellConfirm]);
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ void lds_phase_permute(const LdsLaunch& a, LdsLane& st) {
+  const uint32_t px = (st.pm >> kLdsPhasePermute) & 1u;
+  const uint32_t lane = (uint32_t)st.lane, w0 = (uint32_t)st.wave * 64u;
+#pragma unroll 1
+  for (uint32_t step = 0; step < (uint32_t)kLdsPermSteps; ++step) {
+    const uint32_t map = lds_perm_map(a.seed, st.block, st.rep, step, (uint32_t)st.wave);
+    const uint32_t val = lds_perm_value(a.seed, st.block, st.rep, step, w0 + lane);
+    const uint32_t to = lds_perm_sigma(map, lane);
+    // pull: this lane reads the value of lane sigma(l)
+    const uint32_t pulled =
+        (uint32_t)__builtin_amdgcn_ds_bpermute((int)(to * 4u), (int)val);
+    // push: this lane's value goes to lane sigma(l), so it receives the value
+    // of lane sigma^-1(l)
+    const uint32_t pushed =
+        (uint32_t)__builtin_amdgcn_ds_permute((int)(to * 4u), (int)val);
+    lds_check(a, st, kLdsPhasePermute, step * 2u, (uint32_t)st.tid,
+              lds_perm_value(a.seed, st.block, st.rep, step, w0 + to) ^ px, pulled);
+    lds_check(a, st, kLdsPhasePermute, step * 2u + 1u, (uint32_t)st.tid,
+              lds_perm_value(a.seed, st.block, st.rep, step,
+                             w0 + lds_perm_sigma_inv(map, lane)) ^ px,
+              pushed);
+  }
+}
+#endif  // __gfx950__
+
+// second bound = waves per SIMD: one workgroup per CU
+__global__ void __launch_bounds__(kLdsBlock, 1) lds_integrity_kernel(LdsLaunch a) {
+#if defined(__gfx950__)
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+  const uint32_t hw_id = __builtin_amdgcn_s_getreg(kCovHwRegHwId);
+  const uint32_t xcc_id = __builtin_amdgcn_s_getreg(kCovHwRegXccId);
+  LdsLane st = {};
+  st.key = ((xcc_id & 0xFu) << 8) | ((hw_id >> 8) & 0xFFu);
+  st.block = blockIdx.x;
+  st.tid = (int)threadIdx.x;
+  st.lane = st.tid & 63;
+  st.wave = __builtin_amdgcn_readfirstlane(st.tid >> 6);
+  // test hook: data only
+  st.pm = (a.poison_all || (int)st.key == a.poison_key) ? a.poison_mask : 0u;
+
+  uint32_t s = 0;  // chunk c of step s belongs to wave (c + s) % 4
+#pragma unroll 1
+  for (uint32_t rep = 0; rep < a.reps; ++rep) {
+    st.rep = rep;
+#pragma unroll 1
+    for (int pat = 0; pat <= (int)a.passes; ++pat) {
+      lds_pattern_dispatch<0>(lds, a, st, pat, s++);
+      lds_pattern_dispatch<1>(lds, a, st, pat, s++);
+      lds_pattern_dispatch<2>(lds, a, st, pat, s++);
+    }
+    lds_phase_subword(lds, a, st, s);
+    lds_phase_transpose(lds, a, st, s);
+    lds_phase_dma(lds, a, st, s);
+    lds_phase_atomics(lds, a, st);
+    lds_phase_permute(a, st);
+  }
+
+  // one flush per wave: ballots and shuffles, nothing goes through LDS
+  unsigned wave_fail = 0;
+  for (int b = 0; b < kLdsPhases; ++b)
+    if (__ballot((st.fail >> b) & 1u) != 0) wave_fail |= 1u << b;
+  if (st.bad != 0) {  // on a mismatch, and only then
+    atomicAdd(&a.ctl[kLdsCtlErrors], (unsigned long long)st.bad);
+    atomicOr(&a.ctl[kLdsCtlXor], (unsigned long long)st.bad_xor);
+  }
+  for (int p = 0; p < kLdsPhases; ++p) {
+    uint32_t sum = st.compared[p];
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if (st.lane == 0) atomicAdd(&a.counters[p], (unsigned long long)sum);
+  }
+  if (st.lane == 0 && wave_fail)  // key < kCovKeys by the masks above
+    atomicOr(&a.keys[kCovKeys + st.key], wave_fail);
+  if (st.tid == 0) {
+    atomicAdd(&a.keys[st.key], 1u);
+    a.keys[2 * kCovKeys + st.key] = hw_id;    // raw registers, kept as evidence
+    a.keys[3 * kCovKeys + st.key] = xcc_id;
+  }
+#endif
+}
+
+// Single-wave probe: copy a 16-bit image into LDS, issue one
+// ds_read_b64_tr_b16 with the caller's 64 addresses, return what every lane
+// received.  The host has validated alignment and bounds.
+__global__ void __launch_bounds__(64, 1)
+lds_tr_tile_kernel(const uint16_t* __restrict__ image, uint32_t elems,
+                   const uint32_t* __restrict__ offsets,
+                   uint16_t* __restrict__ out) {
+#if defined(__gfx950__)
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsWords];
+  const uint32_t lane = threadIdx.x;  // one wave of 64
+  uint16_t* l16 = reinterpret_cast<uint16_t*>(lds);
+  for (uint32_t e = lane; e < elems && e < 2u * kLdsWords; e += 64) l16[e] = image[e];
+  __syncthreads();
+  // the loop above has reconverged: EXEC is all ones here
+  uint32_t off = offsets[lane] & ~7u;
+  if (off > (uint32_t)kLdsBytes - 8u) off = (uint32_t)kLdsBytes - 8u;
+  const s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s16x4*)(reinterpret_cast<char*>(lds) + off));
+  for (int q = 0; q < 4; ++q) out[lane * 4 + q] = (uint16_t)r[q];
+#endif
+}
+
+static std::vector<std::vector<int>> lds_tr_tile(
+    int device, const std::vector<uint16_t>& image,
+    const std::vector<int64_t>& lane_byte_offsets) {
+  lds_tr_tile_validate(image.size(), lane_byte_offsets);  // before any HIP call
+  std::vector<uint32_t> offs(lane_byte_offsets.begin(), lane_byte_offsets.end());
+  HIP_CHECK(hipSetDevice(device));
+  DeviceBuf<uint16_t> d_image(image.size()), d_out(64 * 4);
+  DeviceBuf<uint32_t> d_offs(offs.size());
+  d_image.upload(image.data(), image.size());
+  d_offs.upload(offs.data(), offs.size());
+  d_out.fill(0xFF);
+  hipLaunchKernelGGL(lds_tr_tile_kernel, dim3(1), dim3(64), 0, 0, d_image.get(),
+                     (uint32_t)image.size(), d_offs.get(), d_out.get());
+  HIP_CHECK(hipGetLastError());
+  std::vector<uint16_t> h(64 * 4);
+  d_out.download(h.data(), h.size());
+  std::vector<std::vector<int>> out(64, std::vector<int>(4));
+  for (int l = 0; l < 64; ++l)
+    for (int q = 0; q < 4; ++q) out[l][q] = h[l * 4 + q];
+  return out;
+}
+
+struct LdsShape {
+  int reps, passes, max_rounds, blocks, poison_key, poison_word;
+  unsigned poison_mask;
+  uint64_t poison_xor;
+};
+
+// every argument is validated here, before the first HIP call
+static void lds_validate(const std::string& who, const LdsShape& s) {
+  if (s.reps < 1 || s.reps > kLdsMaxReps)
+    throw std::invalid_argument(who + ": reps must be in [1, 4096]");
+  if (s.passes < 1 || s.passes > kLdsMaxPasses)
+    throw std::invalid_argument(who + ": passes must be in [1, 16]");
+  if (s.max_rounds < 1 || s.max_rounds > 64)
+    throw std::invalid_argument(who + ": max_rounds must be in [1, 64]");
+  if (s.blocks < 0 || s.blocks > kLdsMaxBlocks)
+    throw std::invalid_argument(
+        who + ": blocks must be 0 (two per compute unit) or in [1, 65536]");
+  if (s.poison_key < -1 || s.poison_key >= kCovKeys)
+    throw std::invalid_argument(who + ": poison_key out of range");
+  if (s.poison_mask >= (1u << kLdsPhases))
+    throw std::invalid_argument(who + ": poison_mask has 6 bits");
+  if (s.poison_word < -1 || s.poison_word >= kLdsWords)
+    throw std::invalid_argument(who + ": poison_word is -1 or a word below 40960");
+  if (s.poison_xor == 0 || s.poison_xor > 0xFFFFFFFFull)
+    throw std::invalid_argument(who + ": poison_xor is a non-zero 32-bit mask");
+}
+
+static py::dict lds_phase_dict(const uint64_t* v) {
+  py::dict d;
+  for (int p = 0; p < kLdsPhases; ++p) d[kLdsPhaseNames[p]] = v[p];
+  return d;
+}
+
+static py::dict lds_integrity_check(int device, int reps, int passes,
+                                    int max_rounds, uint64_t seed, int blocks,
+                                    int poison_key, unsigned poison_mask,
+                                    bool poison_all, int poison_word,
+                                    uint64_t poison_xor) {
+  const LdsShape s = {reps, passes, max_rounds, blocks, poison_key, poison_word,
+                      poison_mask, poison_xor};
+  lds_validate("lds_integrity_check", s);
+
+  hipDeviceProp_t prop;
+  HIP_CHECK(hipSetDevice(device));
+  HIP_CHECK(hipGetDeviceProperties(&prop, device));
+  const int cus = prop.multiProcessorCount;
+  if (cus < 1 || cus > kCovKeys)
+    throw std::runtime_error("lds_integrity_check: implausible compute unit count");
+  const int grid = blocks > 0 ? blocks : kCovBlocksPerCu * cus;
+
+  const std::vector<uint32_t> h_src = lds_dma_source(seed);
+  DeviceBuf<uint32_t> d_src(h_src.size());
+  DeviceBuf<uint32_t> d_keys((size_t)kLdsKeyPlanes * kCovKeys);
+  DeviceBuf<unsigned long long> d_ctl(kLdsCtlWords), d_counters(kLdsPhases);
+  DeviceBuf<LdsRecord> d_records(kLdsMaxRecords);
+  d_src.upload(h_src.data(), h_src.size());
+  d_keys.fill(0);
+  d_ctl.fill(0);
+  d_counters.fill(0);
+  d_records.fill(0);
+  EventTimer timer;
+
+  LdsLaunch a;
+  a.src = d_src.get();
+  a.keys = d_keys.get();
+  a.ctl = d_ctl.get();
+  a.counters = d_counters.get();
+  a.records = d_records.get();
+  a.seed = seed;
+  a.reps = (uint32_t)reps;
+  a.passes = (uint32_t)passes;
+  a.max_records = kLdsMaxRecords;
+  a.poison_mask = poison_mask;
+  a.poison_xor = (uint32_t)poison_xor;
+  a.poison_key = poison_key;
+  a.poison_all = poison_all ? 1 : 0;
+  a.poison_word = poison_word;
+
+  std::vector<uint32_t> h(d_keys.size());
+  int rounds = 0, cus_covered = 0;
+  double elapsed_ms = 0.0;
+  while (rounds < max_rounds) {
+    // A device or partition that grants less than 160 KiB to a workgroup
+    // rejects the launch: that raises here, it never tests less.  The launch
+    // status decides, not the sharedMemPerBlock property.
+    elapsed_ms += timer.time_ms([&] {
+      hipLaunchKernelGGL(lds_integrity_kernel, dim3(grid), dim3(kLdsBlock), 0, 0, a);
+      HIP_CHECK(hipGetLastError());
+    });
+    ++rounds;
+    d_keys.download(h.data(), h.size());
+    cus_covered = 0;
+    for (int key = 0; key < kCovKeys; ++key) cus_covered += h[key] != 0;
+    if (cus_covered >= cus) break;
+  }
+
+  unsigned long long ctl[kLdsCtlWords], counters[kLdsPhases];
+  d_ctl.download(ctl, kLdsCtlWords);
+  d_counters.download(counters, kLdsPhases);
+  const uint64_t claims = ctl[kLdsCtlClaims];
+  const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)kLdsMaxRecords);
+  std::vector<LdsRecord> recs(kept);
+  if (kept) d_records.download(recs.data(), kept);
+
+  py::list units;
+  for (int key = 0; key < kCovKeys; ++key) {
+    if (h[key] == 0) continue;
+    py::dict u;
+    u["key"] = key;
+    u["xcc"] = key >> 8;
+    u["hw_bits"] = key & 0xFF;
+    u["workgroups"] = h[key];
+    u["fail_mask"] = h[kCovKeys + key];
+    u["hw_id_raw"] = h[2 * kCovKeys + key];
+    u["xcc_id_raw"] = h[3 * kCovKeys + key];
+    units.append(u);
+  }
+  py::list records;
+  for (const LdsRecord& r : recs) {
+    py::dict e;
+    e["key"] = r.key;
+    e["block"] = r.block;
+    e["rep"] = r.rep;
+    e["phase"] = r.phase < (uint32_t)kLdsPhases ? kLdsPhaseNames[r.phase] : "?";
+    e["detail"] = r.detail;
+    e["word"] = r.word;
+    e["expected"] = r.expected;
+    e["got"] = r.got;
+    records.append(e);
+  }
+  uint64_t verified[kLdsPhases], expected[kLdsPhases];
+  for (int p = 0; p < kLdsPhases; ++p) {
+    verified[p] = counters[p];
+    expected[p] = (uint64_t)rounds * (uint64_t)grid * (uint64_t)reps *
+                  lds_phase_items(p, passes);
+  }
+  py::dict out;
+  out["compute_units"] = cus;
+  out["cus_covered"] = cus_covered;
+  out["rounds"] = rounds;
+  out["blocks"] = grid;
+  out["reps"] = reps;
+  out["passes"] = passes;
+  out["seed"] = seed;
+  out["lds_bytes"] = kLdsBytes;
+  out["units"] = units;
+  out["phase_words_verified"] = lds_phase_dict(verified);
+  out["phase_words_expected"] = lds_phase_dict(expected);
+  out["error_count"] = ctl[kLdsCtlErrors];
+  out["xor_or"] = ctl[kLdsCtlXor];
+  out["records"] = records;
+  // a mismatch that found no record slot left, or found them all claimed
+  out["records_dropped"] = ctl[kLdsCtlErrors] - (uint64_t)kept;
+  out["elapsed_ms"] = elapsed_ms;
+  return out;
+}
+
+// host only: no HIP call
+static py::dict lds_integrity_reference(uint64_t seed, int block, int rep,
+                                        int passes) {
+  if (block < 0 || block >= kLdsMaxBlocks || rep < 0 || rep >= kLdsMaxReps)
+    throw std::invalid_argument(
+        "lds_integrity_reference: block is in [0, 65535], rep in [0, 4095]");
+  if (passes < 1 || passes > kLdsMaxPasses)
+    throw std::invalid_argument("lds_integrity_reference: passes must be in [1, 16]");
+  const uint32_t b = (uint32_t)block, r = (uint32_t)rep;
+  static const char* const kWidthNames[3] = {"b32", "b64", "b128"};
+
+  py::dict out;
+  out["lds_words"] = kLdsWords;
+  out["phases"] = std::vector<std::string>(kLdsPhaseNames, kLdsPhaseNames + kLdsPhases);
+  py::list images, widths;
+  for (int pat = 0; pat <= passes; ++pat) {
+    images.append(lds_pattern_image(seed, passes, b, r, pat));
+    py::list w;
+    for (int step = 0; step < 3; ++step)
+      w.append(kWidthNames[lds_pattern_width(pat, step)]);
+    widths.append(w);
+  }
+  out["pattern_images"] = images;  // after the fill of each pattern, checker last
+  out["pattern_widths"] = widths;
+  out["subword_image"] = lds_subword_image(seed, b, r);
+  out["dma_source"] = lds_dma_source(seed);
+  out["dma_image"] = lds_dma_image(seed, b, r);
+  out["transpose_image"] = lds_tr_image(seed, b, r);
+
+  // the last wave-instruction of the 160-byte-row image: its fourth block
+  // ends at byte 163839
+  {
+    const int R = kLdsTrRowBlocks[1];
+    const uint32_t n = kLdsTrBlocks / 4 - 1;
+    std::vector<uint32_t> offs(64);
+    std::vector<std::vector<uint32_t>> lanes(64, std::vector<uint32_t>(4));
+    for (uint32_t l = 0; l < 64; ++l) {
+      const uint32_t blk = 4 * n + (l >> 4), i = l & 15;
+      offs[l] = lds_tr_lane_offset(R, blk, i);
+      for (uint32_t q = 0; q < 4; ++q)
+        lanes[l][q] = lds_tr_elem(seed, b, r, lds_tr_expected_elem(R, blk, i, q));
+    }
+    py::dict t;
+    t["row_stride_bytes"] = 32 * R;
+    t["first_block"] = 4 * n;
+    t["lane_byte_offsets"] = offs;
+    t["lanes"] = lanes;
+    out["transpose"] = t;
+  }
+  {
+    const LdsAtomExpected e = lds_atom_expected(seed, b, r);  // enforces the bound
+    py::dict d;
+    d["add_u32"] = e.add32;
+    d["add_u64"] = e.add64;
+    d["add_f32"] = e.addf;
+    d["add_f32_abs_sum"] = e.addf_abs;
+    d["max_u32"] = e.max32;
+    d["min_u32"] = e.min32;
+    d["xor_u32"] = e.x;
+    d["or_u32"] = e.o;
+    d["and_u32"] = e.a;
+    d["f32_bound"] = kLdsF32Bound;
+    d["cells"] = kLdsAtomCells;
+    d["steps"] = kLdsAtomSteps;
+    out["atomics"] = d;
+  }
+  py::list perm;
+  for (uint32_t step = 0; step < (uint32_t)kLdsPermSteps; ++step) {
+    std::vector<uint32_t> values(kLdsBlock), sigma(kLdsBlock), pulled(kLdsBlock),
+        pushed(kLdsBlock);
+    for (uint32_t t = 0; t < (uint32_t)kLdsBlock; ++t) {
+      const uint32_t wave = t >> 6, lane = t & 63;
+      const uint32_t map = lds_perm_map(seed, b, r, step, wave);
+      values[t] = lds_perm_value(seed, b, r, step, t);
+      sigma[t] = lds_perm_sigma(map, lane);
+      pulled[t] = lds_perm_value(seed, b, r, step, wave * 64 + sigma[t]);
+      pushed[t] = lds_perm_value(seed, b, r, step,
+                                 wave * 64 + lds_perm_sigma_inv(map, lane));
+    }
+    py::dict e;
+    e["values"] = values;
+    e["sigma"] = sigma;
+    e["bpermute"] = pulled;
+    e["permute"] = pushed;
+    perm.append(e);
+  }
+  out["permute"] = perm;
+  return out;
+}
+
 PYBIND11_MODULE(_gpu_validator, m) {
   m.doc() = "MI355X (gfx950) native GPU health validator";
+  m.def("lds_integrity_check", &lds_integrity_check, py::arg("device") = 0,
+        py::arg("reps") = 2, py::arg("passes") = 3, py::arg("max_rounds") = 8,
+        py::arg("seed") = 1ull, py::arg("blocks") = 0, py::arg("poison_key") = -1,
+        py::arg("poison_mask") = 0u, py::arg("poison_all") = false,
+        py::arg("poison_word") = -1, py::arg("poison_xor") = 1ull,
+        "LDS data-integrity check: all 160 KiB of every CU through moving "
+        "inversions in three widths, sub-word stores, transposed reads, direct "
+        "global->LDS loads, the LDS atomic ALU and the permute crossbar, exact, "
+        "coverage counted, failures attributed per CU and word");
+  m.def("lds_integrity_reference", &lds_integrity_reference, py::arg("seed") = 1ull,
+        py::arg("block") = 0, py::arg("rep") = 0, py::arg("passes") = 3,
+        "Host-only: the expected LDS images, one transposed read, the atomic "
+        "totals and the permute results of one workgroup and repetition");
+  m.def("lds_tr_tile", &lds_tr_tile, py::arg("device"), py::arg("image_u16"),
+        py::arg("lane_byte_offsets"),
+        "Run one ds_read_b64_tr_b16 over a caller-supplied 16-bit LDS image "
+        "with 64 caller-supplied byte addresses; returns 64 x 4 raw elements");
   m.def("xcd_fabric_check", &xcd_fabric_check, py::arg("device") = 0,
         py::arg("reps") = 8, py::arg("group") = 16, py::arg("slab_lines") = 8,
         py::arg("cells") = 64, py::arg("blocks") = 0, py::arg("max_rounds") = 8,

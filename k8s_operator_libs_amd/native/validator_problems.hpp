@@ -4,8 +4,9 @@
 //
 // Plain C++17: no HIP and no Python header, so
 // tests/native/validator_problems_selftest.cpp drives all of it stand-alone
-// under AddressSanitizer + UBSan.  The five functions the kernels call as
-// well are marked VALIDATOR_HD.
+// under AddressSanitizer + UBSan.  The functions the kernels call as well are
+// marked VALIDATOR_HD.  The generators of the LDS data-integrity check are in
+// lds_problems.hpp, included at the end.
 
 #pragma once
 
@@ -729,3 +730,9 @@ inline XfAtomExpected xf_atom_expected(uint64_t seed, uint64_t threads, int reps
           " > 2^23; use more cells or fewer reps");
   return e;
 }
+
+// ---------------------------------------------------------------------------
+// LDS data-integrity check: its generators live in a header of their own.
+// ---------------------------------------------------------------------------
+
+#include "lds_problems.hpp"

@@ -28,7 +28,13 @@ Layers:
   hand-offs (agent-scope release, ticket, acquire) between workgroups on
   different XCDs and a device-scope atomics sweep, exact, coverage counted,
   failures attributed per (writer, reader) XCC pair
-  (:func:`summarize_xcd_fabric` is the pure verdict).
+  (:func:`summarize_xcd_fabric` is the pure verdict);
+- :func:`lds_integrity_check` — opt-in LDS data-integrity check: all 160 KiB
+  of every CU through moving inversions in ``b32`` / ``b64`` / ``b128``,
+  sub-word stores, ``ds_read_b64_tr_b16``, direct global->LDS loads, the LDS
+  atomic ALU and the permute crossbar, exact, coverage counted, failures
+  attributed per CU, word and bank (:func:`summarize_lds_integrity` is the
+  pure verdict).
 """
 
 from .gpu_health import (  # noqa: F401
@@ -44,6 +50,10 @@ from .cu_coverage import (  # noqa: F401
 from .hbm_integrity import (  # noqa: F401
     hbm_integrity_check,
     summarize_hbm_integrity,
+)
+from .lds_integrity import (  # noqa: F401
+    lds_integrity_check,
+    summarize_lds_integrity,
 )
 from .mx_matrix import (  # noqa: F401
     mx_matrix_check,

@@ -92,6 +92,7 @@ def gpu_health_check(
     memory_mib: float = 4096.0,
     mx: bool = False,
     fabric: bool = False,
+    lds: bool = False,
 ) -> Dict[str, Any]:
     """Full node GPU health check.  Returns a report dict with a top-level
     ``healthy`` verdict; raises GpuHealthError when ``require_gpu`` and no
@@ -103,7 +104,9 @@ def gpu_health_check(
     its e2m1 / e4m3 burn-in (see :mod:`.mx_matrix`); the verdict is gated on
     the sweep and on each throughput reaching ``MFMA_MIN_TFLOPS``.  ``fabric``
     adds the cross-XCD hand-off and device-scope atomics check (see
-    :mod:`.xcd_fabric`) and gates on it."""
+    :mod:`.xcd_fabric`) and gates on it.  ``lds`` adds the LDS data-integrity
+    check over all 160 KiB of every CU (see :mod:`.lds_integrity`) and gates on
+    it."""
     report: Dict[str, Any] = {"healthy": False, "checks": {}}
     report["checks"]["smi"] = smi_probe()
 
@@ -191,6 +194,16 @@ def gpu_health_check(
         report["checks"]["xcd_fabric"] = fab
         fabric_ok = fab["healthy"]
 
+    lds_integrity_ok = True
+    if lds:
+        # opt-in: all 160 KiB of LDS on every CU, summary without raw units or
+        # records
+        from .lds_integrity import summarize_lds_integrity
+
+        lds_summary = summarize_lds_integrity(native.lds_integrity_check(device))
+        report["checks"]["lds_integrity"] = lds_summary
+        lds_integrity_ok = lds_summary["healthy"]
+
     # multi-GPU nodes: verify every xGMI peer link is up
     xgmi_ok = True
     if probe.get("device_count", 1) > 1:
@@ -211,6 +224,7 @@ def gpu_health_check(
         and memory_ok
         and mx_ok
         and fabric_ok
+        and lds_integrity_ok
     )
     return report
 
@@ -221,7 +235,7 @@ def main() -> int:
     ``--memory`` for the HBM pattern test (``--memory-mib=N`` sets its size
     and implies it; ``N=0`` means all free memory) and ``--mx`` for the MX
     block-scaled matrix sweep and burn-in, ``--fabric`` for the cross-XCD
-    hand-off and atomics check."""
+    hand-off and atomics check, ``--lds`` for the LDS data-integrity check."""
     import sys
 
     memory_kw: Dict[str, Any] = {}
@@ -237,6 +251,7 @@ def main() -> int:
         coverage="--coverage" in sys.argv,
         mx="--mx" in sys.argv,
         fabric="--fabric" in sys.argv,
+        lds="--lds" in sys.argv,
         **memory_kw,
     )
     print(json.dumps(report, indent=2, default=str))  # noqa: T201 (CLI/build output)
