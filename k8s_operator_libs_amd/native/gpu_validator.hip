@@ -37,11 +37,16 @@
 //                           atomics and ds_bpermute / ds_permute, exact,
 //                           attributed per CU and word (opt-in)
 //   lds_tr_tile()         — one ds_read_b64_tr_b16, raw elements returned
+//   host_link_check()     — what crosses the host link: DMA copies both ways,
+//                           zero-copy kernel access, duplex and unaligned
+//                           copies, system-scope atomics on pinned, registered
+//                           and pageable host memory, exact, failing words and
+//                           copy cases recorded (opt-in)
 //
 // This file holds the kernels, the HIP host drivers, the py::dict conversion
 // and the module table.  Device memory and events are owned by the holders in
-// hip_util.hpp (DeviceBuf<T>, EventTimer); the exact problems the checks run
-// (operands, codecs, packed tables, expected results, and the records and
+// hip_util.hpp (DeviceBuf<T>, HostBuf, RegisteredBuf, Stream, EventTimer);
+// the exact problems the checks run (operands, codecs, packed tables, expected results, and the records and
 // constants shared with the kernels) are plain C++ in validator_problems.hpp.
 //
 // Built standalone with hipcc (no torch linkage) via pybind11; the .so lives
@@ -54,6 +59,8 @@
 
 #include <cmath>
 #include <algorithm>
+#include <chrono>
+#include <cstdlib>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -2998,8 +3005,910 @@ static py::dict lds_integrity_reference(uint64_t seed, int block, int rep,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Host-link data-integrity check: bytes that cross the path between host
+// memory and the device (pinning, IOMMU / GART mappings, the copy engines,
+// userptr registration, PCIe AtomicOps) are compared exactly.  Per memory kind
+// (pinned: hipHostMalloc, registered: hipHostRegister of ordinary pages,
+// pageable: malloc) one host buffer H and one device buffer D go through
+//   h2d        CPU fills H with p0, copy H->D, a kernel compares D and writes ~p0
+//   d2h        copy D->H, the CPU compares H with ~p0
+//   zc_read    CPU fills H with p2, a kernel reads H through its device pointer
+//   zc_write   a kernel writes ~p2 into H (16-byte, byte and 16-bit stores),
+//              the CPU compares
+//   duplex     H.lo->D.lo and D.hi->H.hi enqueued on two streams at once
+//   unaligned  464 short copies at odd offsets and lengths, whole destination
+//              slots compared
+//   atomics    system-scope fetch-add, swap and compare-and-swap on pinned
+//              memory while the host thread adds to the same cells
+// Patterns, the copy plan and the atomics operands are in
+// hostlink_problems.hpp; the device-memory steps reuse hbm_pattern_kernel.
+//
+// Counting is as in the HBM check: lanes count what they compared, a workgroup
+// adds its total to a sharded counter once, the host sums the shards per phase
+// and reports them next to the expected count.  Every kernel does a fixed
+// amount of work and exits; the host reads memory a kernel writes only after
+// a synchronise.  The poison hook XORs into expected values, never into
+// memory.  The check sets no environment variable and leaves to the runtime
+// which engine performs a copy.
+// ---------------------------------------------------------------------------
+
+constexpr int kHlBlock = 256;
+constexpr int kHlChunkShift = 7;                 // 128 words: 1 KiB chunks
+constexpr uint64_t kHlSubwordBytes = 1ull << 20;  // sub-word chunks live here
+
+// zc_write: store ~p for vector i (words 2i, 2i + 1).  Inside the first
+// sub_words words (a whole number of chunks) chunk c % 4 == 1 is assembled from
+// byte stores and c % 4 == 3 from 16-bit stores: the owner of vector v of the
+// chunk stores the pieces v, v + 64, v + 128, ... of the chunk, so the eight
+// bytes (four halves) of one word come from eight (four) different lanes and
+// the 64 vector owners of a chunk together store each of its pieces once.
+__device__ __forceinline__ void hostlink_store_vec(const HbmLaunch& a,
+                                                   uint64_t sub_words, uint64_t i) {
+  const uint64_t w0 = 2 * i;
+  if (w0 < sub_words) {
+    const uint64_t c = w0 >> kHlChunkShift, first = c << kHlChunkShift;
+    const uint32_t v = (uint32_t)(i & 63);
+    if ((c & 3) == 1) {
+      uint8_t* bytes = reinterpret_cast<uint8_t*>(a.buf + first);
+      for (uint32_t k = 0; k < 16; ++k) {
+        const uint32_t o = v + 64 * k;  // < 1024
+        const uint64_t p = ~hbm_pattern_value(a.pattern, a.seed, first + (o >> 3));
+        bytes[o] = (uint8_t)(p >> (8 * (o & 7)));
+      }
+      return;
+    }
+    if ((c & 3) == 3) {
+      uint16_t* halves = reinterpret_cast<uint16_t*>(a.buf + first);
+      for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t h = v + 64 * k;  // < 512
+        const uint64_t p = ~hbm_pattern_value(a.pattern, a.seed, first + (h >> 2));
+        halves[h] = (uint16_t)(p >> (16 * (h & 3)));
+      }
+      return;
+    }
+  }
+  u64x2 p;
+  p[0] = ~hbm_pattern_value(a.pattern, a.seed, w0);
+  p[1] = ~hbm_pattern_value(a.pattern, a.seed, w0 + 1);
+  __builtin_nontemporal_store(p, reinterpret_cast<u64x2*>(a.buf) + i);
+}
+
+// a.buf is host memory seen through its device pointer.  WRITE false: compare
+// with p (zc_read); true: write ~p (zc_write).  Shape and counting as in
+// hbm_pattern_kernel: 16-byte nontemporal accesses, 2x unrolled grid-stride
+// body, remainder loop, one thread for an odd last word.  A lane's counter is
+// 32-bit: 2^27 words at the most, over at least 256 threads.
+template <bool WRITE>
+__global__ void __launch_bounds__(kHlBlock)
+hostlink_pattern_kernel(HbmLaunch a, uint64_t sub_words) {
+  __shared__ uint32_t wave_compared[kHlBlock / 64];
+  const u64x2* __restrict__ v = reinterpret_cast<const u64x2*>(a.buf);
+  const uint64_t nvec = a.nwords >> 1;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t compared = 0, bad = 0;
+  uint64_t bad_xor = 0;
+
+  uint64_t i = tid;
+  for (; i + stride < nvec; i += 2 * stride) {
+    if (WRITE) {
+      hostlink_store_vec(a, sub_words, i);
+      hostlink_store_vec(a, sub_words, i + stride);
+    } else {
+      const uint64_t w0 = 2 * i, w1 = 2 * (i + stride);
+      const u64x2 g0 = __builtin_nontemporal_load(&v[i]);
+      const u64x2 g1 = __builtin_nontemporal_load(&v[i + stride]);
+      const uint64_t x0 = hbm_diff(a, w0, g0[0], 0);
+      const uint64_t x1 = hbm_diff(a, w0 + 1, g0[1], 0);
+      const uint64_t x2 = hbm_diff(a, w1, g1[0], 0);
+      const uint64_t x3 = hbm_diff(a, w1 + 1, g1[1], 0);
+      compared += 4;
+      if ((x0 | x1 | x2 | x3) != 0) {
+        hbm_report(a, w0, g0[0], x0, bad, bad_xor);
+        hbm_report(a, w0 + 1, g0[1], x1, bad, bad_xor);
+        hbm_report(a, w1, g1[0], x2, bad, bad_xor);
+        hbm_report(a, w1 + 1, g1[1], x3, bad, bad_xor);
+      }
+    }
+  }
+  for (; i < nvec; i += stride) {
+    if (WRITE) {
+      hostlink_store_vec(a, sub_words, i);
+    } else {
+      const uint64_t w0 = 2 * i;
+      const u64x2 g0 = __builtin_nontemporal_load(&v[i]);
+      const uint64_t x0 = hbm_diff(a, w0, g0[0], 0);
+      const uint64_t x1 = hbm_diff(a, w0 + 1, g0[1], 0);
+      compared += 2;
+      if ((x0 | x1) != 0) {
+        hbm_report(a, w0, g0[0], x0, bad, bad_xor);
+        hbm_report(a, w0 + 1, g0[1], x1, bad, bad_xor);
+      }
+    }
+  }
+  if ((a.nwords & 1ull) && tid == 0) {  // scalar tail: the odd last word
+    const uint64_t t = a.nwords - 1;
+    if (WRITE) {
+      a.buf[t] = ~hbm_pattern_value(a.pattern, a.seed, t);
+    } else {
+      const uint64_t got = a.buf[t];
+      ++compared;
+      hbm_report(a, t, got, hbm_diff(a, t, got, 0), bad, bad_xor);
+    }
+  }
+
+  if (!WRITE) {
+    if (bad != 0) {  // on a mismatch, and only then
+      atomicAdd(&a.ctl[kHbmCtlErrors], (unsigned long long)bad);
+      atomicOr(&a.ctl[kHbmCtlXor], (unsigned long long)bad_xor);
+    }
+    uint32_t sum = compared;
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_compared[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0;
+      for (int w = 0; w < kHlBlock / 64; ++w) total += wave_compared[w];
+      atomicAdd(&a.shards[(blockIdx.x & (kHbmShards - 1)) * kHbmShardStride],
+                total);
+    }
+  }
+}
+
+// The atomics tables, all in one pinned host buffer: 64 cells and four
+// counters, each on a 128-byte line of its own, then seen[] and olds[].
+struct alignas(128) HlCell {
+  uint64_t add64, swap64, claim64, confirm64;
+  uint32_t add32, claim32, confirm32;
+};
+struct alignas(128) HlLine {
+  unsigned long long v;
+};
+constexpr int kHlLineTicket = 0, kHlLineWinners32 = 1, kHlLineWinners64 = 2,
+              kHlLineTicketRange = 3, kHlLines = 4;
+
+struct HlAtomics {
+  HlCell* cells;
+  HlLine* lines;
+  uint32_t* seen;   // [threads]: id + 1 of the thread that drew ticket t
+  uint64_t* olds;   // [threads]: what thread id got back from its exchange
+  uint64_t seed;
+  uint32_t reps, threads;
+};
+
+// Fetch-add, swap and compare-and-swap, 32 and 64 bit, all system scope and
+// all on host memory.  Fixed work: nothing here waits for another thread or
+// for the host, which adds to the same cells while this runs.
+__global__ void __launch_bounds__(kHostlinkAtomBlock)
+hostlink_atomics_kernel(HlAtomics a) {
+  const uint32_t id = blockIdx.x * kHostlinkAtomBlock + threadIdx.x;
+  for (uint32_t r = 0; r < a.reps; ++r) {
+    const HostlinkAtomVals v = hostlink_atom_vals(a.seed, id, r);
+    HlCell& c = a.cells[(id + r) % kHostlinkAtomCells];
+    __hip_atomic_fetch_add(&c.add32, v.add32, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_fetch_add(&c.add64, v.add64, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  // the ticket is range-checked before it is used as an index
+  const unsigned long long ticket =
+      __hip_atomic_fetch_add(&a.lines[kHlLineTicket].v, 1ull, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
+  if (ticket < a.threads)
+    a.seen[ticket] = id + 1;
+  else
+    __hip_atomic_fetch_add(&a.lines[kHlLineTicketRange].v, 1ull, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+  a.olds[id] = __hip_atomic_exchange(&a.cells[id % kHostlinkAtomCells].swap64,
+                                     (uint64_t)id + 1, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_SYSTEM);
+  HlCell& k = a.cells[id % kHostlinkClaimCells];
+  uint32_t free32 = 0;
+  if (__hip_atomic_compare_exchange_strong(&k.claim32, &free32, id + 1,
+                                           __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_SYSTEM)) {
+    k.confirm32 = id + 1;
+    __hip_atomic_fetch_add(&a.lines[kHlLineWinners32].v, 1ull, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  uint64_t free64 = 0;
+  if (__hip_atomic_compare_exchange_strong(&k.claim64, &free64, (uint64_t)id + 1,
+                                           __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_SYSTEM)) {
+    k.confirm64 = (uint64_t)id + 1;
+    __hip_atomic_fetch_add(&a.lines[kHlLineWinners64].v, 1ull, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// One host buffer of a memory kind.  dev is null for pageable memory.
+struct HlHostMem {
+  HostBuf pinned;
+  RegisteredBuf registered;
+  void* pageable = nullptr;
+  uint8_t* host = nullptr;
+  uint8_t* dev = nullptr;
+  HlHostMem(int kind, size_t bytes) {
+    if (kind == kHostlinkPinned) {
+      pinned = HostBuf(bytes);
+      host = static_cast<uint8_t*>(pinned.get());
+      dev = static_cast<uint8_t*>(pinned.device());
+    } else if (kind == kHostlinkRegistered) {
+      registered = RegisteredBuf(bytes);
+      host = static_cast<uint8_t*>(registered.get());
+      dev = static_cast<uint8_t*>(registered.device());
+    } else {
+      pageable = std::malloc(bytes);
+      if (!pageable) throw std::bad_alloc();
+      host = static_cast<uint8_t*>(pageable);
+    }
+  }
+  HlHostMem(const HlHostMem&) = delete;
+  HlHostMem& operator=(const HlHostMem&) = delete;
+  ~HlHostMem() { std::free(pageable); }
+};
+
+struct HlPhase {
+  bool ran = false;
+  uint64_t compared = 0, expected = 0, errors = 0;
+  double ms = 0.0;          // the whole phase, host fills and compares included
+  double link_ms = 0.0;     // the step that crossed the link
+  double link_bytes = 0.0;  // and what it moved
+};
+
+static double hl_ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now() - t0).count();
+}
+
+// What a run accumulates over all kinds and phases.  The record cap is shared:
+// a phase may keep what the phases before it left of max_records.
+struct HlRun {
+  int max_records = 0;
+  uint64_t error_count = 0, xor_or = 0, dropped = 0;
+  py::list records;
+  size_t room() const { return (size_t)max_records - py::len(records); }
+};
+
+static py::dict hl_word_record(int kind, int phase, const char* side,
+                               uint64_t word, uint64_t expected, uint64_t got) {
+  py::dict e;
+  e["kind"] = kHostlinkKindNames[kind];
+  e["phase"] = kHostlinkPhaseNames[phase];
+  e["side"] = side;
+  e["word"] = word;
+  e["byte_offset"] = 8 * word;
+  e["expected"] = expected;
+  e["got"] = got;
+  py::list bits;
+  for (int b = 0; b < 64; ++b)
+    if (((expected ^ got) >> b) & 1ull) bits.append(b);
+  e["flipped_bits"] = bits;
+  return e;
+}
+
+// the result tables of the kernels that compare on the device
+struct HlDeviceTables {
+  DeviceBuf<unsigned long long> ctl{kHbmCtlWords};
+  DeviceBuf<unsigned long long> shards{(size_t)kHbmShards * kHbmShardStride};
+  DeviceBuf<HbmRecord> records;
+  explicit HlDeviceTables(int max_records)
+      : records((size_t)std::max(1, max_records)) {
+    ctl.fill(0);
+    shards.fill(0);
+    records.fill(0);
+  }
+  // after a synchronise: move what the kernels of one phase counted and
+  // recorded into `ph` and `run`, and zero the tables for the next phase
+  void take(int kind, int phase, HlPhase& ph, HlRun& run) {
+    unsigned long long c[kHbmCtlWords];
+    std::vector<unsigned long long> sh(shards.size());
+    ctl.download(c, kHbmCtlWords);
+    shards.download(sh.data(), sh.size());
+    for (int s = 0; s < kHbmShards; ++s)
+      ph.compared += sh[(size_t)s * kHbmShardStride];
+    ph.errors += c[kHbmCtlErrors];
+    run.error_count += c[kHbmCtlErrors];
+    run.xor_or |= c[kHbmCtlXor];
+    const size_t kept =
+        (size_t)std::min<uint64_t>(c[kHbmCtlClaims], (uint64_t)run.room());
+    std::vector<HbmRecord> recs(kept);
+    if (kept) records.download(recs.data(), kept);
+    for (const HbmRecord& r : recs)
+      run.records.append(
+          hl_word_record(kind, phase, "device", r.word, r.expected, r.got));
+    run.dropped += c[kHbmCtlClaims] - kept;
+    ctl.fill(0);
+    shards.fill(0);
+  }
+};
+
+static void hl_take_host(int kind, int phase, const HostlinkTally& t, HlPhase& ph,
+                         HlRun& run) {
+  ph.compared += t.compared;
+  ph.errors += t.errors;
+  run.error_count += t.errors;
+  run.xor_or |= t.xor_or;
+  run.dropped += t.dropped;
+  for (const HostlinkWordRecord& r : t.records)
+    run.records.append(
+        hl_word_record(kind, phase, "host", r.word, r.expected, r.got));
+}
+
+static void hl_atom_mismatch(HlRun& run, HlPhase& ph, const char* comparison,
+                             const char* op, int cell, py::object expected,
+                             py::object got) {
+  ++ph.errors;
+  ++run.error_count;
+  if (run.room() == 0) {
+    ++run.dropped;
+    return;
+  }
+  py::dict e;
+  e["kind"] = kHostlinkKindNames[kHostlinkPinned];
+  e["phase"] = kHostlinkPhaseNames[kHostlinkAtomics];
+  e["side"] = "host";
+  e["comparison"] = comparison;
+  e["op"] = op;
+  e["cell"] = cell;
+  e["expected"] = expected;
+  e["got"] = got;
+  run.records.append(e);
+}
+
+// The atomics phase on a pinned buffer of its own; returns its tables.
+static py::dict hl_run_atomics(int blocks, int reps, uint64_t host_adds,
+                               uint64_t seed, bool poisoned, uint64_t poison_xor,
+                               HlPhase& ph, HlRun& run) {
+  const uint32_t threads = (uint32_t)blocks * kHostlinkAtomBlock;
+  const HostlinkAtomExpected e =
+      hostlink_atom_expected(seed, threads, reps, host_adds);
+  const size_t cells_b = sizeof(HlCell) * kHostlinkAtomCells;
+  const size_t lines_b = sizeof(HlLine) * kHlLines;
+  const size_t olds_b = sizeof(uint64_t) * threads;
+  const size_t seen_b = sizeof(uint32_t) * threads;
+  HostBuf mem(cells_b + lines_b + olds_b + seen_b);
+  std::memset(mem.get(), 0, mem.size());
+  uint8_t* h = static_cast<uint8_t*>(mem.get());
+  uint8_t* d = static_cast<uint8_t*>(mem.device());
+  HlCell* cells = reinterpret_cast<HlCell*>(h);
+  HlLine* lines = reinterpret_cast<HlLine*>(h + cells_b);
+  const uint64_t* olds = reinterpret_cast<const uint64_t*>(h + cells_b + lines_b);
+  const uint32_t* seen =
+      reinterpret_cast<const uint32_t*>(h + cells_b + lines_b + olds_b);
+
+  HlAtomics a;
+  a.cells = reinterpret_cast<HlCell*>(d);
+  a.lines = reinterpret_cast<HlLine*>(d + cells_b);
+  a.olds = reinterpret_cast<uint64_t*>(d + cells_b + lines_b);
+  a.seen = reinterpret_cast<uint32_t*>(d + cells_b + lines_b + olds_b);
+  a.seed = seed;
+  a.reps = (uint32_t)reps;
+  a.threads = threads;
+  const auto t0 = std::chrono::steady_clock::now();
+  hipLaunchKernelGGL(hostlink_atomics_kernel, dim3(blocks),
+                     dim3(kHostlinkAtomBlock), 0, 0, a);
+  HIP_CHECK(hipGetLastError());
+  // the host's own adds to the same cells: fixed work, nobody waits
+  for (uint64_t j = 0; j < host_adds; ++j) {
+    const HostlinkAtomVals v = hostlink_atom_vals(seed, kHostlinkHostId + j, 0);
+    HlCell& c = cells[j % kHostlinkAtomCells];
+    __atomic_fetch_add(&c.add32, v.add32, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&c.add64, v.add64, __ATOMIC_RELAXED);
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  ph.link_ms = hl_ms_since(t0);
+
+  std::vector<uint32_t> add32(kHostlinkAtomCells);
+  std::vector<uint64_t> add64(kHostlinkAtomCells);
+  for (int c = 0; c < kHostlinkAtomCells; ++c) {
+    add32[c] = cells[c].add32;
+    add64[c] = cells[c].add64;
+    // test hook: data only, the expected value of add32 cell 0
+    const uint32_t w32 =
+        e.add32[c] ^ (poisoned && c == 0 ? (uint32_t)poison_xor : 0u);
+    if (add32[c] != w32)
+      hl_atom_mismatch(run, ph, "add_u32", "add_u32", c, py::int_(w32),
+                       py::int_(add32[c]));
+    if (add64[c] != e.add64[c])
+      hl_atom_mismatch(run, ph, "add_u64", "add_u64", c, py::int_(e.add64[c]),
+                       py::int_(add64[c]));
+  }
+  ph.compared += 2 * kHostlinkAtomCells;
+
+  // every ticket drawn exactly once: counter == threads and no hole in seen
+  const uint64_t counter = lines[kHlLineTicket].v;
+  const uint64_t out_of_range = lines[kHlLineTicketRange].v;
+  if (counter != threads)
+    hl_atom_mismatch(run, ph, "tickets", "fetch_add_u64", -1, py::int_(threads),
+                     py::int_(counter));
+  if (out_of_range != 0)
+    hl_atom_mismatch(run, ph, "tickets", "ticket_range", -1, py::int_(0),
+                     py::int_(out_of_range));
+  uint64_t holes = 0;
+  for (uint32_t t = 0; t < threads; ++t) holes += seen[t] == 0;
+  if (holes != 0)
+    hl_atom_mismatch(run, ph, "tickets", "seen_holes", -1, py::int_(0),
+                     py::int_(holes));
+  ph.compared += 2 + threads;
+
+  // swap: what came back plus what stayed is {0 x 64} and {1 .. threads}
+  std::vector<uint64_t> bag(olds, olds + threads);
+  for (int c = 0; c < kHostlinkAtomCells; ++c) bag.push_back(cells[c].swap64);
+  std::sort(bag.begin(), bag.end());
+  uint64_t swap_bad = 0;
+  for (size_t i = 0; i < bag.size(); ++i) {
+    const uint64_t want =
+        i < (size_t)kHostlinkAtomCells ? 0 : i - kHostlinkAtomCells + 1;
+    if (bag[i] != want && swap_bad++ == 0)
+      hl_atom_mismatch(run, ph, "swap", "swap_u64", -1, py::int_(want),
+                       py::int_(bag[i]));
+  }
+  if (swap_bad > 1) {  // the first is recorded, the rest only counted
+    ph.errors += swap_bad - 1;
+    run.error_count += swap_bad - 1;
+    run.dropped += swap_bad - 1;
+  }
+  ph.compared += bag.size();
+
+  // compare-and-swap: one winner per cell and width, who confirmed it
+  std::vector<uint64_t> claim32(kHostlinkClaimCells), confirm32(kHostlinkClaimCells),
+      claim64(kHostlinkClaimCells), confirm64(kHostlinkClaimCells);
+  for (int c = 0; c < kHostlinkClaimCells; ++c) {
+    claim32[c] = cells[c].claim32;
+    confirm32[c] = cells[c].confirm32;
+    claim64[c] = cells[c].claim64;
+    confirm64[c] = cells[c].confirm64;
+    if (claim32[c] == 0 || claim32[c] != confirm32[c])
+      hl_atom_mismatch(run, ph, "cas", "cas_u32", c, py::int_(claim32[c]),
+                       py::int_(confirm32[c]));
+    if (claim64[c] == 0 || claim64[c] != confirm64[c])
+      hl_atom_mismatch(run, ph, "cas", "cas_u64", c, py::int_(claim64[c]),
+                       py::int_(confirm64[c]));
+  }
+  const uint64_t winners32 = lines[kHlLineWinners32].v;
+  const uint64_t winners64 = lines[kHlLineWinners64].v;
+  const uint64_t want_winners = std::min<uint64_t>(threads, kHostlinkClaimCells);
+  if (winners32 != want_winners)
+    hl_atom_mismatch(run, ph, "cas", "winners_u32", -1, py::int_(want_winners),
+                     py::int_(winners32));
+  if (winners64 != want_winners)
+    hl_atom_mismatch(run, ph, "cas", "winners_u64", -1, py::int_(want_winners),
+                     py::int_(winners64));
+  ph.compared += 2 * kHostlinkClaimCells + 2;
+  ph.expected = hostlink_atom_items(threads);
+
+  py::dict out;
+  out["blocks"] = blocks;
+  out["threads"] = threads;
+  out["reps"] = reps;
+  out["host_adds"] = host_adds;
+  out["add32"] = add32;
+  out["add64"] = add64;
+  out["expected_add32"] = e.add32;
+  out["expected_add64"] = e.add64;
+  out["ticket_counter"] = counter;
+  out["tickets_out_of_range"] = out_of_range;
+  out["seen_holes"] = holes;
+  out["swap_mismatches"] = swap_bad;
+  out["claim32"] = claim32;
+  out["confirm32"] = confirm32;
+  out["claim64"] = claim64;
+  out["confirm64"] = confirm64;
+  out["winners32"] = winners32;
+  out["winners64"] = winners64;
+  return out;
+}
+
+static py::dict host_link_plan() {
+  const HostlinkPlan plan = hostlink_plan();
+  py::list cases;
+  for (const HostlinkCase& c : plan.cases) {
+    py::dict e;
+    e["case"] = c.index;
+    e["direction"] = kHostlinkDirectionNames[c.direction];
+    e["len"] = c.len;
+    e["src_off"] = c.src_off;
+    e["dst_off"] = c.dst_off;
+    e["src_pos"] = c.src_pos();
+    e["dst_pos"] = c.dst_pos();
+    cases.append(e);
+  }
+  py::dict out;
+  out["slot_bytes"] = plan.slot_bytes;
+  out["guard"] = plan.guard;
+  out["cases"] = cases;
+  return out;
+}
+
+static py::dict host_link_reference(uint64_t seed, uint64_t threads, int reps,
+                                    int64_t host_adds) {
+  // host only: no HIP call
+  if (threads > (uint64_t)kHostlinkMaxAtomBlocks * kHostlinkAtomBlock)
+    throw std::invalid_argument("host_link_reference: threads is at most 262144");
+  if (reps < 1 || reps > kHostlinkMaxReps)
+    throw std::invalid_argument("host_link_reference: reps must be in [1, 16]");
+  if (host_adds < 0 || host_adds > kHostlinkMaxHostAdds ||
+      host_adds % kHostlinkAtomCells != 0)
+    throw std::invalid_argument(
+        "host_link_reference: host_adds must be a multiple of 64 in [0, 2^20]");
+  const HostlinkAtomExpected e =
+      hostlink_atom_expected(seed, threads, reps, (uint64_t)host_adds);
+  py::dict out;
+  out["add32"] = e.add32;
+  out["add64"] = e.add64;
+  out["device_add32"] = e.device32;
+  out["device_add64"] = e.device64;
+  out["host_add32"] = e.host32;
+  out["host_add64"] = e.host64;
+  out["items"] = hostlink_atom_items(threads);
+  return out;
+}
+
+static py::dict host_link_check(int device, uint64_t nbytes, uint64_t seed,
+                                const std::vector<std::string>& kinds, int blocks,
+                                int atomics_blocks, int reps, int64_t host_adds,
+                                int max_records, unsigned poison_mask,
+                                int poison_kind, int64_t poison_word,
+                                int64_t poison_case, uint64_t poison_xor) {
+  // every argument is validated before the first HIP call
+  HostlinkShape shape{nbytes,      hostlink_kind_list(kinds), blocks,
+                      atomics_blocks, reps,                   host_adds,
+                      max_records, poison_mask,               poison_kind,
+                      poison_word, poison_case,               poison_xor};
+  hostlink_validate(shape);
+
+  HIP_CHECK(hipSetDevice(device));
+  int cus = 0, native_atomics = 0;
+  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                  device));
+  HIP_CHECK(hipDeviceGetAttribute(
+      &native_atomics, hipDeviceAttributeHostNativeAtomicSupported, device));
+  const int grid = blocks > 0 ? blocks : 4 * cus;
+  const int atom_grid =
+      atomics_blocks > 0 ? atomics_blocks : std::min(cus, kHostlinkMaxAtomBlocks);
+  const uint64_t words = nbytes / 8, lo = words / 2;
+  const uint64_t sub_words = (std::min(nbytes, kHlSubwordBytes) >> 10)
+                             << kHlChunkShift;
+  const HostlinkPlan plan = hostlink_plan();
+  const auto run_t0 = std::chrono::steady_clock::now();
+
+  HlRun run;
+  run.max_records = max_records;
+  HlDeviceTables tables(max_records);
+  Stream s1, s2;
+  Event e1a, e1b, e2a, e2b;
+  unsigned fail_mask = 0;
+  py::dict kinds_out, atomics_out;
+  bool atomics_ran = false;
+  {
+    // One 4 KiB copy each way on each stream between two scratch buffers, so
+    // the rate of the first phase does not carry the runtime's first-use
+    // set-up of a stream.  No checked buffer is touched.
+    HostBuf warm_h(4096);
+    DeviceBuf<uint8_t> warm_d(4096);
+    std::memset(warm_h.get(), 0, 4096);
+    for (hipStream_t s : {s1.s, s2.s}) {
+      HIP_CHECK(hipMemcpyAsync(warm_d.get(), warm_h.get(), 4096,
+                               hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(warm_h.get(), warm_d.get(), 4096,
+                               hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+  }
+
+  for (const int kind : shape.kinds) {
+    const unsigned runs = hostlink_kind_phases(kind);
+    const bool poison_here = poison_kind < 0 || poison_kind == kind;
+    const auto poisoned = [&](int phase) {
+      return poison_here && ((poison_mask >> phase) & 1u);
+    };
+    const auto pword = [&](int phase) -> int64_t {
+      return poisoned(phase) ? poison_word : -1;
+    };
+    const auto pseed = [&](int phase) {
+      return hostlink_seed(seed, kind, hostlink_data_phase(phase));
+    };
+    HlPhase phases[kHostlinkPhases];
+    bool overlap = false;
+
+    // a failed allocation or registration raises: never silently test less
+    HlHostMem hmem(kind, (size_t)nbytes);
+    DeviceBuf<uint64_t> dbuf((size_t)words);
+    uint64_t* H = reinterpret_cast<uint64_t*>(hmem.host);
+    uint64_t* D = dbuf.get();
+
+    // pinned and registered memory is copied on the check's own stream,
+    // pageable memory with a plain hipMemcpy; both return when the copy is done
+    const auto copy = [&](void* dst, const void* src, size_t n, hipMemcpyKind dir) {
+      if (kind == kHostlinkPageable) {
+        HIP_CHECK(hipMemcpy(dst, src, n, dir));
+      } else {
+        HIP_CHECK(hipMemcpyAsync(dst, src, n, dir, s1.s));
+        HIP_CHECK(hipStreamSynchronize(s1.s));
+      }
+    };
+    // hbm_pattern_kernel over device words [base, base + n) of D
+    const auto device_pass = [&](int hbm_kind, uint64_t base, uint64_t n,
+                                 int phase) {
+      HbmLaunch a;
+      a.buf = D + base;
+      a.nwords = n;
+      a.base = base;
+      a.seed = pseed(phase);
+      a.poison_xor = poison_xor;
+      a.poison_stride = 0;
+      a.poison_word = pword(phase);
+      a.ctl = tables.ctl.get();
+      a.shards = tables.shards.get();
+      a.records = tables.records.get();
+      a.max_records = (uint32_t)run.room();
+      a.verify_index = (uint32_t)phase;
+      a.pattern = kHbmPatternHash;
+      hbm_launch(hbm_kind, a);
+    };
+    // hostlink_pattern_kernel over all of H through its device pointer
+    const auto host_pass = [&](bool write, int phase) {
+      HbmLaunch a;
+      a.buf = reinterpret_cast<uint64_t*>(hmem.dev);
+      a.nwords = words;
+      a.base = 0;
+      a.seed = pseed(phase);
+      a.poison_xor = poison_xor;
+      a.poison_stride = 0;
+      a.poison_word = write ? -1 : pword(phase);
+      a.ctl = tables.ctl.get();
+      a.shards = tables.shards.get();
+      a.records = tables.records.get();
+      a.max_records = (uint32_t)run.room();
+      a.verify_index = (uint32_t)phase;
+      a.pattern = kHbmPatternHash;
+      if (write)
+        hipLaunchKernelGGL(hostlink_pattern_kernel<true>, dim3(grid),
+                           dim3(kHlBlock), 0, 0, a, sub_words);
+      else
+        hipLaunchKernelGGL(hostlink_pattern_kernel<false>, dim3(grid),
+                           dim3(kHlBlock), 0, 0, a, sub_words);
+      HIP_CHECK(hipGetLastError());
+    };
+    const auto host_verify = [&](int phase, uint64_t first, uint64_t n) {
+      HostlinkTally t;
+      hostlink_verify(H + first, first, n, pseed(phase),
+                      hostlink_data_inverted(phase), pword(phase), poison_xor,
+                      run.room(), t);
+      hl_take_host(kind, phase, t, phases[phase], run);
+    };
+    const auto timed = [&](HlPhase& ph, double bytes, auto&& work) {
+      const auto t0 = std::chrono::steady_clock::now();
+      work();
+      ph.link_ms += hl_ms_since(t0);
+      ph.link_bytes += bytes;
+    };
+
+    {  // bit 0, h2d
+      HlPhase& ph = phases[kHostlinkH2d];
+      const auto t0 = std::chrono::steady_clock::now();
+      ph.ran = true;
+      ph.expected = words;
+      hostlink_fill(H, 0, words, pseed(kHostlinkH2d), false);
+      timed(ph, (double)nbytes, [&] { copy(D, H, nbytes, hipMemcpyHostToDevice); });
+      device_pass(kHbmVerifyInvert, 0, words, kHostlinkH2d);
+      HIP_CHECK(hipDeviceSynchronize());
+      tables.take(kind, kHostlinkH2d, ph, run);
+      ph.ms = hl_ms_since(t0);
+    }
+    {  // bit 1, d2h: H still holds p0, D holds ~p0
+      HlPhase& ph = phases[kHostlinkD2h];
+      const auto t0 = std::chrono::steady_clock::now();
+      ph.ran = true;
+      ph.expected = words;
+      timed(ph, (double)nbytes, [&] { copy(H, D, nbytes, hipMemcpyDeviceToHost); });
+      host_verify(kHostlinkD2h, 0, words);
+      ph.ms = hl_ms_since(t0);
+    }
+    if (runs & 1u << kHostlinkZcRead) {  // bit 2
+      HlPhase& ph = phases[kHostlinkZcRead];
+      const auto t0 = std::chrono::steady_clock::now();
+      ph.ran = true;
+      ph.expected = words;
+      hostlink_fill(H, 0, words, pseed(kHostlinkZcRead), false);
+      timed(ph, (double)nbytes, [&] {
+        host_pass(false, kHostlinkZcRead);
+        HIP_CHECK(hipDeviceSynchronize());
+      });
+      tables.take(kind, kHostlinkZcRead, ph, run);
+      ph.ms = hl_ms_since(t0);
+    }
+    if (runs & 1u << kHostlinkZcWrite) {  // bit 3: H holds p2 until the kernel ran
+      HlPhase& ph = phases[kHostlinkZcWrite];
+      const auto t0 = std::chrono::steady_clock::now();
+      ph.ran = true;
+      ph.expected = words;
+      timed(ph, (double)nbytes, [&] {
+        host_pass(true, kHostlinkZcWrite);
+        HIP_CHECK(hipDeviceSynchronize());
+      });
+      host_verify(kHostlinkZcWrite, 0, words);
+      ph.ms = hl_ms_since(t0);
+    }
+    if (runs & 1u << kHostlinkDuplex) {  // bit 4: H.hi holds ~p2, D.lo holds ~p0
+      HlPhase& ph = phases[kHostlinkDuplex];
+      const auto t0 = std::chrono::steady_clock::now();
+      ph.ran = true;
+      ph.expected = words;
+      hostlink_fill(H, 0, lo, pseed(kHostlinkDuplex), false);
+      // fill D.hi; hbm_pattern_kernel's 16-byte stores need an even first
+      // word, so an odd one is filled by a launch of its own (its scalar tail)
+      const uint64_t even = lo + (lo & 1ull);
+      if (lo & 1ull) device_pass(kHbmFill, lo, 1, kHostlinkDuplex);
+      if (even < words) device_pass(kHbmFill, even, words - even, kHostlinkDuplex);
+      HIP_CHECK(hipDeviceSynchronize());
+      timed(ph, (double)nbytes, [&] {
+        HIP_CHECK(hipEventRecord(e1a.ev, s1.s));
+        HIP_CHECK(hipMemcpyAsync(D, H, 8 * lo, hipMemcpyHostToDevice, s1.s));
+        HIP_CHECK(hipEventRecord(e1b.ev, s1.s));
+        HIP_CHECK(hipEventRecord(e2a.ev, s2.s));
+        HIP_CHECK(hipMemcpyAsync(H + lo, D + lo, 8 * (words - lo),
+                                 hipMemcpyDeviceToHost, s2.s));
+        HIP_CHECK(hipEventRecord(e2b.ev, s2.s));
+        HIP_CHECK(hipStreamSynchronize(s1.s));
+        HIP_CHECK(hipStreamSynchronize(s2.s));
+      });
+      // reported, never judged: did the two copies run at the same time?
+      float len1 = 0.f, start2 = 0.f, len2 = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&len1, e1a.ev, e1b.ev));
+      HIP_CHECK(hipEventElapsedTime(&start2, e1a.ev, e2a.ev));
+      HIP_CHECK(hipEventElapsedTime(&len2, e2a.ev, e2b.ev));
+      overlap = start2 < len1 && start2 + len2 > 0.f;
+      // the hook acts on the side that compares poison_word: the kernel sees
+      // only words below lo, the host only the rest
+      device_pass(kHbmVerifyInvert, 0, lo, kHostlinkDuplex);
+      HIP_CHECK(hipDeviceSynchronize());
+      tables.take(kind, kHostlinkDuplex, ph, run);
+      host_verify(kHostlinkDuplex, lo, words - lo);
+      ph.ms = hl_ms_since(t0);
+    }
+    {  // bit 5, unaligned
+      HlPhase& ph = phases[kHostlinkUnaligned];
+      const auto t0 = std::chrono::steady_clock::now();
+      ph.ran = true;
+      ph.expected = (uint64_t)plan.cases.size() * plan.slot_bytes;
+      const uint64_t src_seed = hostlink_seed(seed, kind, kHostlinkUnaligned);
+      const uint64_t bg_seed = hostlink_seed(seed, kind, kHostlinkBackground);
+      HlHostMem slots(kind, 2 * plan.slot_bytes);
+      DeviceBuf<uint8_t> dslot(plan.slot_bytes);
+      uint8_t* ha = slots.host;                    // the source image
+      uint8_t* hb = slots.host + plan.slot_bytes;  // background / destination
+      uint8_t* ds = dslot.get();
+      HostlinkSlotTally t;
+      for (const HostlinkCase& c : plan.cases) {
+        hostlink_slot_fill(ha, src_seed, c.index);
+        hostlink_slot_fill(hb, bg_seed, c.index);
+        if (c.direction == 0) {
+          // the destination slot is on the device: whole-slot aligned copies
+          // set it and bring it back
+          copy(ds, hb, plan.slot_bytes, hipMemcpyHostToDevice);
+          timed(ph, (double)c.len, [&] {
+            copy(ds + c.dst_pos(), ha + c.src_pos(), c.len, hipMemcpyHostToDevice);
+          });
+          copy(hb, ds, plan.slot_bytes, hipMemcpyDeviceToHost);
+        } else {
+          copy(ds, ha, plan.slot_bytes, hipMemcpyHostToDevice);
+          timed(ph, (double)c.len, [&] {
+            copy(hb + c.dst_pos(), ds + c.src_pos(), c.len, hipMemcpyDeviceToHost);
+          });
+        }
+        const bool hit = poisoned(kHostlinkUnaligned) && c.index == poison_case;
+        const size_t before = t.records.size();
+        hostlink_slot_compare(hb, c, src_seed, bg_seed,
+                              hit ? (uint8_t)poison_xor : (uint8_t)0,
+                              before + run.room(), t);
+        for (size_t r = before; r < t.records.size(); ++r) {
+          const HostlinkByteRecord& b = t.records[r];
+          py::dict e;
+          e["kind"] = kHostlinkKindNames[kind];
+          e["phase"] = kHostlinkPhaseNames[kHostlinkUnaligned];
+          e["side"] = "host";
+          e["case"] = c.index;
+          e["direction"] = kHostlinkDirectionNames[c.direction];
+          e["src_off"] = c.src_off;
+          e["dst_off"] = c.dst_off;
+          e["len"] = c.len;
+          e["byte_offset"] = b.offset;
+          e["expected"] = (int)b.expected;
+          e["got"] = (int)b.got;
+          py::list bits;
+          for (int k = 0; k < 8; ++k)
+            if (((b.expected ^ b.got) >> k) & 1) bits.append(k);
+          e["flipped_bits"] = bits;
+          run.records.append(e);
+        }
+      }
+      ph.compared = t.compared;
+      ph.errors = t.errors;
+      run.error_count += t.errors;
+      run.xor_or |= t.xor_or;
+      run.dropped += t.dropped;
+      ph.ms = hl_ms_since(t0);
+    }
+    if ((runs & 1u << kHostlinkAtomics) && native_atomics != 0) {  // bit 6
+      HlPhase& ph = phases[kHostlinkAtomics];
+      const auto t0 = std::chrono::steady_clock::now();
+      ph.ran = true;
+      atomics_out = hl_run_atomics(atom_grid, reps, (uint64_t)host_adds, seed,
+                                   poisoned(kHostlinkAtomics), poison_xor, ph, run);
+      atomics_ran = true;
+      ph.ms = hl_ms_since(t0);
+    }
+
+    unsigned kind_mask = 0;
+    py::dict phase_dict;
+    for (int p = 0; p < kHostlinkPhases; ++p) {
+      const HlPhase& ph = phases[p];
+      if (!ph.ran) continue;
+      if (ph.errors != 0) kind_mask |= 1u << p;
+      py::dict e;
+      e["compared"] = ph.compared;
+      e["expected"] = ph.expected;
+      e["errors"] = ph.errors;
+      e["elapsed_ms"] = ph.ms;
+      e["link_ms"] = ph.link_ms;
+      e["gbps"] = ph.link_ms > 0.0 ? ph.link_bytes / 1e9 / (ph.link_ms / 1e3) : 0.0;
+      phase_dict[kHostlinkPhaseNames[p]] = e;
+    }
+    fail_mask |= kind_mask;
+    py::dict k;
+    k["fail_mask"] = kind_mask;
+    k["phases"] = phase_dict;
+    if (phases[kHostlinkDuplex].ran) k["duplex_overlap"] = overlap;
+    kinds_out[kHostlinkKindNames[kind]] = k;
+  }
+
+  py::dict out;
+  out["bytes"] = nbytes;
+  out["words"] = words;
+  out["seed"] = seed;
+  out["blocks"] = grid;
+  out["plan_cases"] = plan.cases.size();
+  out["slot_bytes"] = plan.slot_bytes;
+  out["kinds"] = kinds_out;
+  out["fail_mask"] = fail_mask;
+  out["error_count"] = run.error_count;
+  out["xor_or"] = run.xor_or;
+  out["records"] = run.records;
+  out["records_dropped"] = run.dropped;
+  out["atomics_supported"] = native_atomics != 0;
+  if (atomics_ran)
+    out["atomics"] = atomics_out;
+  else
+    out["atomics"] = py::none();
+  out["elapsed_ms"] = hl_ms_since(run_t0);
+  return out;
+}
+
+
 PYBIND11_MODULE(_gpu_validator, m) {
   m.doc() = "MI355X (gfx950) native GPU health validator";
+  m.def("host_link_check", &host_link_check, py::arg("device") = 0,
+        py::arg("nbytes") = 64ull << 20, py::arg("seed") = 1ull,
+        py::arg("kinds") =
+            std::vector<std::string>{"pinned", "registered", "pageable"},
+        py::arg("blocks") = 0, py::arg("atomics_blocks") = 0, py::arg("reps") = 2,
+        py::arg("host_adds") = (int64_t)4096, py::arg("max_records") = 64,
+        py::arg("poison_mask") = 0u, py::arg("poison_kind") = -1,
+        py::arg("poison_word") = (int64_t)-1, py::arg("poison_case") = (int64_t)-1,
+        py::arg("poison_xor") = 1ull,
+        "Host-link data-integrity check: DMA copies in both directions, "
+        "zero-copy kernel access, duplex copies, unaligned copies and "
+        "system-scope atomics on pinned, registered and pageable host memory, "
+        "exact, coverage counted, failing words and cases recorded");
+  m.def("host_link_plan", &host_link_plan,
+        "Host-only: the unaligned copy plan of host_link_check");
+  m.def("host_link_reference", &host_link_reference, py::arg("seed") = 1ull,
+        py::arg("threads") = 0ull, py::arg("reps") = 2,
+        py::arg("host_adds") = (int64_t)4096,
+        "Host-only: the expected add cells of the host-link atomics phase");
   m.def("lds_integrity_check", &lds_integrity_check, py::arg("device") = 0,
         py::arg("reps") = 2, py::arg("passes") = 3, py::arg("max_rounds") = 8,
         py::arg("seed") = 1ull, py::arg("blocks") = 0, py::arg("poison_key") = -1,

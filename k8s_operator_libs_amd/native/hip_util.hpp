@@ -2,14 +2,18 @@
 //
 // HIP_CHECK throws, so everything a check allocates is owned by one of these:
 // nothing leaks when a HIP call fails half-way through a check, which is what
-// happens on the unhealthy node the validator exists for.  Nothing here pools,
-// caches or outlives the call that made it.
+// happens on the unhealthy node the validator exists for.  Device memory
+// (DeviceBuf), pinned and registered host memory (HostBuf, RegisteredBuf),
+// streams and events.  Nothing here pools, caches or outlives the call that
+// made it.
 
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdlib>
+#include <new>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -72,6 +76,105 @@ class DeviceBuf {
   }
   void* ptr_ = nullptr;
   size_t n_ = 0;
+};
+
+// `bytes` of pinned host memory from hipHostMalloc.  Move-only; device() is
+// the address a kernel uses for it.
+class HostBuf {
+ public:
+  HostBuf() = default;
+  explicit HostBuf(size_t bytes) : bytes_(bytes) {
+    HIP_CHECK(hipHostMalloc(&ptr_, bytes, hipHostMallocDefault));
+  }
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  HostBuf(HostBuf&& o) noexcept { swap(o); }
+  HostBuf& operator=(HostBuf&& o) noexcept {
+    swap(o);
+    return *this;
+  }
+  ~HostBuf() {
+    if (ptr_) (void)hipHostFree(ptr_);
+  }
+  void* get() const { return ptr_; }
+  size_t size() const { return bytes_; }
+  void* device() const {
+    void* d = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer(&d, ptr_, 0));
+    return d;
+  }
+
+ private:
+  void swap(HostBuf& o) noexcept {
+    std::swap(ptr_, o.ptr_);
+    std::swap(bytes_, o.bytes_);
+  }
+  void* ptr_ = nullptr;
+  size_t bytes_ = 0;
+};
+
+// `bytes` of page-aligned ordinary memory, registered with hipHostRegister
+// (the userptr path).  Move-only; the destructor unregisters, then frees.
+class RegisteredBuf {
+ public:
+  RegisteredBuf() = default;
+  explicit RegisteredBuf(size_t bytes) : bytes_(bytes) {
+    const size_t page = 4096;
+    if (posix_memalign(&ptr_, page, (bytes + page - 1) / page * page) != 0) {
+      ptr_ = nullptr;
+      throw std::bad_alloc();
+    }
+    const hipError_t e = hipHostRegister(ptr_, bytes, hipHostRegisterDefault);
+    if (e != hipSuccess) {
+      std::free(ptr_);
+      ptr_ = nullptr;
+      throw std::runtime_error(std::string("HIP error at hipHostRegister: ") +
+                               hipGetErrorString(e));
+    }
+  }
+  RegisteredBuf(const RegisteredBuf&) = delete;
+  RegisteredBuf& operator=(const RegisteredBuf&) = delete;
+  RegisteredBuf(RegisteredBuf&& o) noexcept { swap(o); }
+  RegisteredBuf& operator=(RegisteredBuf&& o) noexcept {
+    swap(o);
+    return *this;
+  }
+  ~RegisteredBuf() {
+    if (!ptr_) return;
+    (void)hipHostUnregister(ptr_);
+    std::free(ptr_);
+  }
+  void* get() const { return ptr_; }
+  size_t size() const { return bytes_; }
+  void* device() const {
+    void* d = nullptr;
+    HIP_CHECK(hipHostGetDevicePointer(&d, ptr_, 0));
+    return d;
+  }
+
+ private:
+  void swap(RegisteredBuf& o) noexcept {
+    std::swap(ptr_, o.ptr_);
+    std::swap(bytes_, o.bytes_);
+  }
+  void* ptr_ = nullptr;
+  size_t bytes_ = 0;
+};
+
+// A non-blocking stream: it does not synchronise with the null stream.
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() { HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  Stream(Stream&& o) noexcept { std::swap(s, o.s); }
+  Stream& operator=(Stream&& o) noexcept {
+    std::swap(s, o.s);
+    return *this;
+  }
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
 };
 
 struct Event {

@@ -34,7 +34,12 @@ Layers:
   sub-word stores, ``ds_read_b64_tr_b16``, direct global->LDS loads, the LDS
   atomic ALU and the permute crossbar, exact, coverage counted, failures
   attributed per CU, word and bank (:func:`summarize_lds_integrity` is the
-  pure verdict).
+  pure verdict);
+- :func:`host_link_check` — opt-in host-link data-integrity check: DMA copies
+  in both directions, zero-copy kernel access, duplex and unaligned copies on
+  pinned, registered and pageable host memory and system-scope atomics on
+  pinned memory, exact, coverage counted, failing words and copy cases
+  recorded (:func:`summarize_host_link` is the pure verdict).
 """
 
 from .gpu_health import (  # noqa: F401
@@ -50,6 +55,10 @@ from .cu_coverage import (  # noqa: F401
 from .hbm_integrity import (  # noqa: F401
     hbm_integrity_check,
     summarize_hbm_integrity,
+)
+from .host_link import (  # noqa: F401
+    host_link_check,
+    summarize_host_link,
 )
 from .lds_integrity import (  # noqa: F401
     lds_integrity_check,

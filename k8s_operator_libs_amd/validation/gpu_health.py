@@ -93,6 +93,8 @@ def gpu_health_check(
     mx: bool = False,
     fabric: bool = False,
     lds: bool = False,
+    hostlink: bool = False,
+    hostlink_mib: float = 64.0,
 ) -> Dict[str, Any]:
     """Full node GPU health check.  Returns a report dict with a top-level
     ``healthy`` verdict; raises GpuHealthError when ``require_gpu`` and no
@@ -106,7 +108,10 @@ def gpu_health_check(
     adds the cross-XCD hand-off and device-scope atomics check (see
     :mod:`.xcd_fabric`) and gates on it.  ``lds`` adds the LDS data-integrity
     check over all 160 KiB of every CU (see :mod:`.lds_integrity`) and gates on
-    it."""
+    it.  ``hostlink`` adds the host-link data-integrity check with
+    ``hostlink_mib`` MiB per buffer (DMA copies, zero-copy access and
+    system-scope atomics on host memory; see :mod:`.host_link`) and gates on it
+    as well."""
     report: Dict[str, Any] = {"healthy": False, "checks": {}}
     report["checks"]["smi"] = smi_probe()
 
@@ -204,6 +209,19 @@ def gpu_health_check(
         report["checks"]["lds_integrity"] = lds_summary
         lds_integrity_ok = lds_summary["healthy"]
 
+    host_link_ok = True
+    if hostlink:
+        # opt-in: what crosses the host link compared exactly, summary without
+        # raw records
+        from .hbm_integrity import mib_to_bytes
+        from .host_link import summarize_host_link
+
+        link = summarize_host_link(
+            native.host_link_check(device, mib_to_bytes(hostlink_mib))
+        )
+        report["checks"]["host_link"] = link
+        host_link_ok = link["healthy"]
+
     # multi-GPU nodes: verify every xGMI peer link is up
     xgmi_ok = True
     if probe.get("device_count", 1) > 1:
@@ -225,6 +243,7 @@ def gpu_health_check(
         and mx_ok
         and fabric_ok
         and lds_integrity_ok
+        and host_link_ok
     )
     return report
 
@@ -235,16 +254,23 @@ def main() -> int:
     ``--memory`` for the HBM pattern test (``--memory-mib=N`` sets its size
     and implies it; ``N=0`` means all free memory) and ``--mx`` for the MX
     block-scaled matrix sweep and burn-in, ``--fabric`` for the cross-XCD
-    hand-off and atomics check, ``--lds`` for the LDS data-integrity check."""
+    hand-off and atomics check, ``--lds`` for the LDS data-integrity check and
+    ``--hostlink`` for the host-link data-integrity check (``--hostlink-mib=N``
+    sets its buffer size and implies it)."""
     import sys
 
-    memory_kw: Dict[str, Any] = {}
+    sized_kw: Dict[str, Any] = {}
     for arg in sys.argv[1:]:
         if arg == "--memory":
-            memory_kw["memory"] = True
+            sized_kw["memory"] = True
         elif arg.startswith("--memory-mib="):
-            memory_kw["memory"] = True
-            memory_kw["memory_mib"] = float(arg.split("=", 1)[1])
+            sized_kw["memory"] = True
+            sized_kw["memory_mib"] = float(arg.split("=", 1)[1])
+        elif arg == "--hostlink":
+            sized_kw["hostlink"] = True
+        elif arg.startswith("--hostlink-mib="):
+            sized_kw["hostlink"] = True
+            sized_kw["hostlink_mib"] = float(arg.split("=", 1)[1])
     report = gpu_health_check(
         require_gpu=True,
         deep="--deep" in sys.argv,
@@ -252,7 +278,7 @@ def main() -> int:
         mx="--mx" in sys.argv,
         fabric="--fabric" in sys.argv,
         lds="--lds" in sys.argv,
-        **memory_kw,
+        **sized_kw,
     )
     print(json.dumps(report, indent=2, default=str))  # noqa: T201 (CLI/build output)
     return 0 if report["healthy"] else 1
