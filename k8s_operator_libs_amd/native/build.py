@@ -19,6 +19,7 @@ SOURCES = (
     os.path.join(PKG_DIR, "validator_problems.hpp"),
     os.path.join(PKG_DIR, "lds_problems.hpp"),
     os.path.join(PKG_DIR, "hostlink_problems.hpp"),
+    os.path.join(PKG_DIR, "valu_problems.hpp"),
 )
 OUTPUT = os.path.join(PKG_DIR, "_gpu_validator.so")
 JSONOPS_SOURCE = os.path.join(PKG_DIR, "jsonops.cpp")

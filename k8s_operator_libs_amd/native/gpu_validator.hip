@@ -37,6 +37,12 @@
 //                           atomics and ds_bpermute / ds_permute, exact,
 //                           attributed per CU and word (opt-in)
 //   lds_tr_tile()         — one ds_read_b64_tr_b16, raw elements returned
+//   valu_coverage_check() — the vector ALU on every CU and SIMD: f32 / f64 /
+//                           f16 arithmetic, integer, conversions (bf16, fp8,
+//                           bf8, fp4) and cross-lane ops bit-exact against a
+//                           host reference, transcendentals by consensus of
+//                           all SIMDs, compares counted (opt-in sweep)
+//   valu_probe()          — one vector instruction on one wave, raw results
 //   host_link_check()     — what crosses the host link: DMA copies both ways,
 //                           zero-copy kernel access, duplex and unaligned
 //                           copies, system-scope atomics on pinned, registered
@@ -65,6 +71,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "hip_util.hpp"
@@ -584,12 +591,15 @@ static py::dict cu_coverage_reference() {
 // mx_coverage_check: argument validation before the first HIP call, table
 // upload, bounded relaunch until every CU and SIMD has been seen, and the
 // per-slot result table.  `launch(cus, tab, slots)` enqueues one round of the
-// sweep's kernel on a grid of kCovBlocksPerCu x CUs workgroups.
-template <typename Launch>
+// sweep's kernel on a grid of kCovBlocksPerCu x CUs workgroups.  A sweep with
+// buffers of its own sized by the CU count allocates them in `prepare(cus)`,
+// which runs once, after the device is selected and before the first launch.
+template <typename Launch, typename Prepare>
 static py::dict cov_run_sweep(const std::string& who, int device, int reps,
                               int max_rounds, int poison_key,
                               unsigned poison_mask, int mask_bits,
-                              const std::vector<uint32_t>& tab, Launch launch) {
+                              const std::vector<uint32_t>& tab, Launch launch,
+                              Prepare prepare) {
   if (reps < 1 || reps > 4096)
     throw std::invalid_argument(who + ": reps must be in [1, 4096]");
   if (max_rounds < 1 || max_rounds > 64)
@@ -614,6 +624,7 @@ static py::dict cov_run_sweep(const std::string& who, int device, int reps,
   DeviceBuf<uint32_t> d_slots((size_t)4 * kCovSlots);  // waves | fail | hw_id | xcc_id
   d_tab.upload(tab.data(), tab.size());
   d_slots.fill(0);
+  prepare(cus);
   EventTimer timer;
 
   std::vector<uint32_t> h(d_slots.size());
@@ -669,6 +680,15 @@ static py::dict cov_run_sweep(const std::string& who, int device, int reps,
   out["units"] = units;
   out["elapsed_ms"] = elapsed_ms;
   return out;
+}
+
+template <typename Launch>
+static py::dict cov_run_sweep(const std::string& who, int device, int reps,
+                              int max_rounds, int poison_key,
+                              unsigned poison_mask, int mask_bits,
+                              const std::vector<uint32_t>& tab, Launch launch) {
+  return cov_run_sweep(who, device, reps, max_rounds, poison_key, poison_mask,
+                       mask_bits, tab, launch, [](int) {});
 }
 
 static py::dict cu_coverage_check(int device, int reps, int max_rounds,
@@ -3887,9 +3907,570 @@ static py::dict host_link_check(int device, uint64_t nbytes, uint64_t seed,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Vector-ALU check.  Every other sweep uses the VALU only to compare what
+// another unit produced; this one runs the table of vector instructions of
+// valu_problems.hpp (VALU_OPS) in every wave of a grid that fills the device.
+// Groups 0..5 compare bit-exactly against the host reference; group 6 (raw
+// transcendentals, stochastic rounding, v_prng_b32) has no host expectation
+// and requires that every lane of every wave ends with the same digest.
+//
+// valu_eval<KIND, IMM> is the device side of the list of ValuKind: three
+// 64-bit operands in, one 64-bit result out, the same convention as
+// valu_ref_lane / valu_ref_wave.  The cross-lane kinds need EXEC all ones:
+// they are only ever evaluated in wave-uniform control flow (the set loop of
+// the sweep, the uniform op switch of the probe).
+//
+// Built on the frame of cu_coverage_kernel: same grid, launch bounds, 64 KiB
+// LDS claim, placement key and slot scheme, fixed work per wave.  New here:
+// every compare is counted (seven 64-bit counters, the host checks them
+// against waves x reps x items), every wave leaves a digest record, and the
+// first kValuMaxRecords mismatches are recorded.
+// ---------------------------------------------------------------------------
+
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+
+__device__ __forceinline__ uint32_t valu_dlo(uint64_t v) { return (uint32_t)v; }
+__device__ __forceinline__ uint32_t valu_dhi(uint64_t v) { return (uint32_t)(v >> 32); }
+__device__ __forceinline__ uint64_t valu_dpack(uint32_t lo, uint32_t hi) {
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+__device__ __forceinline__ f32x2 valu_df2(uint64_t v) {
+  return f32x2{__uint_as_float(valu_dlo(v)), __uint_as_float(valu_dhi(v))};
+}
+__device__ __forceinline__ uint64_t valu_dbits(f32x2 v) {
+  return valu_dpack(__float_as_uint(v.x), __float_as_uint(v.y));
+}
+
+template <int KIND, int IMM>
+__device__ __forceinline__ uint64_t valu_eval(uint64_t a, uint64_t b, uint64_t c) {
+#if defined(__gfx950__)
+// the separate multiplies and adds must stay separate
+#pragma clang fp contract(off)
+  const uint32_t al = valu_dlo(a), ah = valu_dhi(a), bl = valu_dlo(b),
+                 cl = valu_dlo(c), ch = valu_dhi(c);
+  const float fa = __uint_as_float(al), fb = __uint_as_float(bl),
+              fc = __uint_as_float(cl);
+  // f32
+  if constexpr (KIND == kVkFmaF32) return __float_as_uint(__builtin_fmaf(fa, fb, fc));
+  else if constexpr (KIND == kVkAddF32) return __float_as_uint(fa + fb);
+  else if constexpr (KIND == kVkMulF32) return __float_as_uint(fa * fb);
+  else if constexpr (KIND == kVkPkFmaF32)
+    return valu_dbits(__builtin_elementwise_fma(valu_df2(a), valu_df2(b), valu_df2(c)));
+  else if constexpr (KIND == kVkPkAddF32) return valu_dbits(valu_df2(a) + valu_df2(b));
+  else if constexpr (KIND == kVkPkMulF32) return valu_dbits(valu_df2(a) * valu_df2(b));
+  else if constexpr (KIND == kVkMinF32) return __float_as_uint(__builtin_fminf(fa, fb));
+  else if constexpr (KIND == kVkMaxF32) return __float_as_uint(__builtin_fmaxf(fa, fb));
+  else if constexpr (KIND == kVkMed3F32)
+    return __float_as_uint(__builtin_amdgcn_fmed3f(fa, fb, fc));
+  else if constexpr (KIND == kVkLdexpF32)
+    return __float_as_uint(__builtin_ldexpf(fa, (int)bl));
+  else if constexpr (KIND == kVkFrexpMantF32)
+    return __float_as_uint(__builtin_amdgcn_frexp_mantf(fa));
+  else if constexpr (KIND == kVkRndneF32) return __float_as_uint(__builtin_rintf(fa));
+  // f64
+  else if constexpr (KIND == kVkFmaF64)
+    return (uint64_t)__double_as_longlong(__builtin_fma(
+        __longlong_as_double((long long)a), __longlong_as_double((long long)b),
+        __longlong_as_double((long long)c)));
+  else if constexpr (KIND == kVkAddF64)
+    return (uint64_t)__double_as_longlong(__longlong_as_double((long long)a) +
+                                          __longlong_as_double((long long)b));
+  else if constexpr (KIND == kVkMulF64)
+    return (uint64_t)__double_as_longlong(__longlong_as_double((long long)a) *
+                                          __longlong_as_double((long long)b));
+  else if constexpr (KIND == kVkLdexpF64)
+    return (uint64_t)__double_as_longlong(
+        __builtin_ldexp(__longlong_as_double((long long)a), (int)bl));
+  // f16
+  else if constexpr (KIND == kVkPkFmaF16)
+    return __builtin_bit_cast(
+        uint32_t, __builtin_elementwise_fma(__builtin_bit_cast(f16x2, al),
+                                            __builtin_bit_cast(f16x2, bl),
+                                            __builtin_bit_cast(f16x2, cl)));
+  else if constexpr (KIND == kVkPkAddF16)
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2, al) +
+                                            __builtin_bit_cast(f16x2, bl));
+  else if constexpr (KIND == kVkPkMulF16)
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2, al) *
+                                            __builtin_bit_cast(f16x2, bl));
+  else if constexpr (KIND == kVkDot2F16)
+    return __float_as_uint(__builtin_amdgcn_fdot2(
+        __builtin_bit_cast(f16x2, al), __builtin_bit_cast(f16x2, bl), fc, false));
+  else if constexpr (KIND == kVkDot2Bf16)
+    return __float_as_uint(__builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_bit_cast(bf16x2, al), __builtin_bit_cast(bf16x2, bl), fc, false));
+  // int
+  else if constexpr (KIND == kVkMadU64U32) return (uint64_t)al * bl + c;
+  else if constexpr (KIND == kVkMulHiU32) return __umulhi(al, bl);
+  else if constexpr (KIND == kVkMulLoU32) return al * bl;
+  else if constexpr (KIND == kVkMulI24) return (uint32_t)__mul24((int)al, (int)bl);
+  // hipcc adds 64-bit integers with v_lshl_add_u64 and folds a bit select
+  // into v_bitop3_b32; the carry chain and v_bfi_b32 are asked for by name
+  else if constexpr (KIND == kVkAddU64) {
+    uint32_t lo, hi;
+    asm volatile("v_add_co_u32 %0, vcc, %2, %4\n\tv_addc_co_u32 %1, vcc, %3, %5, vcc"
+                 : "=&v"(lo), "=v"(hi)
+                 : "v"(al), "v"(ah), "v"(bl), "v"(valu_dhi(b))
+                 : "vcc");
+    return valu_dpack(lo, hi);
+  } else if constexpr (KIND == kVkSubU64) {
+    uint32_t lo, hi;
+    asm volatile("v_sub_co_u32 %0, vcc, %2, %4\n\tv_subb_co_u32 %1, vcc, %3, %5, vcc"
+                 : "=&v"(lo), "=v"(hi)
+                 : "v"(al), "v"(ah), "v"(bl), "v"(valu_dhi(b))
+                 : "vcc");
+    return valu_dpack(lo, hi);
+  }
+  else if constexpr (KIND == kVkLshlB32) return al << (bl & 31u);
+  else if constexpr (KIND == kVkLshrB32) return al >> (bl & 31u);
+  else if constexpr (KIND == kVkAshrI32) return (uint32_t)((int32_t)al >> (bl & 31u));
+  else if constexpr (KIND == kVkLshlB64) return a << (bl & 63u);
+  else if constexpr (KIND == kVkLshrB64) return a >> (bl & 63u);
+  else if constexpr (KIND == kVkAshrI64) return (uint64_t)((int64_t)a >> (bl & 63u));
+  else if constexpr (KIND == kVkBfeU32) return __builtin_amdgcn_ubfe(al, bl & 31u, cl & 31u);
+  else if constexpr (KIND == kVkBfiB32) {
+    uint32_t r;
+    asm volatile("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(al), "v"(bl), "v"(cl));
+    return r;
+  }
+  else if constexpr (KIND == kVkPermB32) return __builtin_amdgcn_perm(al, bl, cl);
+  else if constexpr (KIND == kVkAlignbitB32) return __builtin_amdgcn_alignbit(al, bl, cl);
+  else if constexpr (KIND == kVkSadU8) return __builtin_amdgcn_sad_u8(al, bl, cl);
+  else if constexpr (KIND == kVkBcntU32) return (uint32_t)__builtin_popcount(al) + bl;
+  else if constexpr (KIND == kVkFfbhU32) return (uint32_t)__clz((int)al);
+  else if constexpr (KIND == kVkBfrevB32) return __brev(al);
+  else if constexpr (KIND == kVkBitop3B32) return (uint32_t)__builtin_amdgcn_bitop3_b32(al, bl, cl, IMM);
+  else if constexpr (KIND == kVkDot4I8)
+    return (uint32_t)__builtin_amdgcn_sdot4((int)al, (int)bl, (int)cl, false);
+  else if constexpr (KIND == kVkDot4U8) return __builtin_amdgcn_udot4(al, bl, cl, false);
+  else if constexpr (KIND == kVkCmpSelect) return (int32_t)al < (int32_t)bl ? cl : ch;
+  // convert
+  else if constexpr (KIND == kVkCvtF16F32)
+    return __builtin_bit_cast(uint16_t, (_Float16)fa);
+  else if constexpr (KIND == kVkCvtPkBf16F32)
+    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)fa) |
+           (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)__uint_as_float(ah)) << 16;
+  else if constexpr (KIND == kVkCvtI32F32) return (uint32_t)(int32_t)fa;
+  else if constexpr (KIND == kVkCvtU32F32) return (uint32_t)fa;
+  else if constexpr (KIND == kVkCvtF32I32) return __float_as_uint((float)(int32_t)al);
+  else if constexpr (KIND == kVkCvtF32U32) return __float_as_uint((float)al);
+  else if constexpr (KIND == kVkCvtPkFp8F32)
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(fa, __uint_as_float(ah), (int)cl, IMM != 0);
+  else if constexpr (KIND == kVkCvtPkBf8F32)
+    return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(fa, __uint_as_float(ah), (int)cl, IMM != 0);
+  else if constexpr (KIND == kVkCvtF32Fp8)
+    return __float_as_uint(__builtin_amdgcn_cvt_f32_fp8((int)al, IMM));
+  else if constexpr (KIND == kVkCvtF32Bf8)
+    return __float_as_uint(__builtin_amdgcn_cvt_f32_bf8((int)al, IMM));
+  else if constexpr (KIND == kVkCvtScalePkF32Fp4)
+    return valu_dbits(__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(al, fb, IMM));
+  else if constexpr (KIND == kVkCvtScalePkFp4F32)
+    return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(cl, fa, __uint_as_float(ah), fb, IMM);
+  // crosslane: a is the source, b is `old` / the second register
+  else if constexpr (KIND == kVkDpp)
+    return (uint32_t)__builtin_amdgcn_update_dpp(
+        (int)bl, (int)al, IMM & 0xFFF, kValuDppRowMask[IMM >> 12],
+        kValuDppBankMask[IMM >> 12], (IMM >> 12) != 0);
+  else if constexpr (KIND == kVkReadlane) {
+    const uint32_t r0 = __builtin_amdgcn_readlane((int)al, kValuReadLanes[0]);
+    const uint32_t r1 = __builtin_amdgcn_readlane((int)al, kValuReadLanes[1]);
+    const uint32_t r2 = __builtin_amdgcn_readlane((int)al, kValuReadLanes[2]);
+    const uint32_t r3 = __builtin_amdgcn_readlane((int)al, kValuReadLanes[3]);
+    const int q = (int)(__lane_id() & 3u);
+    return q == 0 ? r0 : q == 1 ? r1 : q == 2 ? r2 : r3;
+  } else if constexpr (KIND == kVkReadfirstlane)
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)al);
+  else if constexpr (KIND == kVkPermlane16Swap) {
+    const auto r = __builtin_amdgcn_permlane16_swap(al, bl, false, false);
+    return valu_dpack(r[0], r[1]);
+  } else if constexpr (KIND == kVkPermlane32Swap) {
+    const auto r = __builtin_amdgcn_permlane32_swap(al, bl, false, false);
+    return valu_dpack(r[0], r[1]);
+  } else if constexpr (KIND == kVkMbcnt)
+    return __builtin_amdgcn_mbcnt_hi(ah, __builtin_amdgcn_mbcnt_lo(al, bl));
+  else if constexpr (KIND == kVkCmpMask) return (uint64_t)__ballot(al < bl);
+  // consensus: the raw instructions, no refinement sequence
+  else if constexpr (KIND == kVkExpF32) return __float_as_uint(__builtin_amdgcn_exp2f(fa));
+  else if constexpr (KIND == kVkLogF32) return __float_as_uint(__builtin_amdgcn_logf(fa));
+  else if constexpr (KIND == kVkRcpF32) return __float_as_uint(__builtin_amdgcn_rcpf(fa));
+  else if constexpr (KIND == kVkRsqF32) return __float_as_uint(__builtin_amdgcn_rsqf(fa));
+  else if constexpr (KIND == kVkSqrtF32) return __float_as_uint(__builtin_amdgcn_sqrtf(fa));
+  else if constexpr (KIND == kVkSinF32) return __float_as_uint(__builtin_amdgcn_sinf(fa));
+  else if constexpr (KIND == kVkCosF32) return __float_as_uint(__builtin_amdgcn_cosf(fa));
+  else if constexpr (KIND == kVkRcpF64)
+    return (uint64_t)__double_as_longlong(
+        __builtin_amdgcn_rcp(__longlong_as_double((long long)a)));
+  else if constexpr (KIND == kVkRsqF64)
+    return (uint64_t)__double_as_longlong(
+        __builtin_amdgcn_rsq(__longlong_as_double((long long)a)));
+  else if constexpr (KIND == kVkCvtSrFp8F32)
+    return (uint32_t)__builtin_amdgcn_cvt_sr_fp8_f32(fa, (int)bl, 0, 0);
+  else if constexpr (KIND == kVkPrngB32) return __builtin_amdgcn_prng_b32(al);
+  else static_assert(KIND < 0, "valu_eval: kind without a device implementation");
+#else
+  return 0;
+#endif
+}
+
+struct ValuRecord {
+  uint32_t key, simd, group, op, set, lane, rep, pad;
+  uint64_t expected, got;
+};
+
+constexpr int kValuCtlErrors = kValuGroups, kValuCtlWords = kValuGroups + 1;
+constexpr int kValuWaveRecWords = 1 + kValuConsOps;  // slot + 1 | digests
+
+struct ValuLaunch {
+  const uint32_t* tab;
+  uint32_t* slots;      // waves | fail | hw_id | xcc_id, as cov_run_sweep keeps them
+  uint64_t* ctl;        // compared[kValuGroups] | error count
+  ValuRecord* records;  // the first kValuMaxRecords mismatches
+  uint64_t* wave_recs;  // [round][block][wave][kValuWaveRecWords]
+  int reps, poison_key, poison_all, round;
+  unsigned poison_mask;
+};
+
+struct ValuWave {
+  uint32_t key, simd, fail;
+  uint32_t count[kValuGroups];
+  uint64_t digest[kValuConsOps];
+};
+
+__device__ __noinline__ void valu_mismatch(uint64_t* ctl, ValuRecord* records,
+                                           uint32_t key,
+                                           uint32_t simd, int group, int op, int set,
+                                           int lane, int rep, uint64_t expected,
+                                           uint64_t got) {
+  const uint64_t n = atomicAdd((unsigned long long*)&ctl[kValuCtlErrors], 1ull);
+  if (n >= (uint64_t)kValuMaxRecords) return;
+  ValuRecord& r = records[n];  // n < kValuMaxRecords, the size of the array
+  r.key = key, r.simd = simd, r.group = (uint32_t)group, r.op = (uint32_t)op;
+  r.set = (uint32_t)set, r.lane = (uint32_t)lane, r.rep = (uint32_t)rep, r.pad = 0;
+  r.expected = expected, r.got = got;
+}
+
+template <int OP>
+__device__ __forceinline__ void valu_step(const ValuLaunch& L, int lane, int rep,
+                                          unsigned pm, ValuWave& w) {
+#if defined(__gfx950__)
+  constexpr int KIND = kValuOpKind[OP], IMM = kValuOpImm[OP], G = kValuOpGroup[OP];
+  // volatile: operands and expected words are re-read from global memory
+  // every repetition, so neither the op nor the compare can be hoisted; the
+  // lane's base is opaque to the optimizer, or the address of every op's
+  // records is hoisted out of the repetition loop and spills
+  const uint32_t* lane_base = L.tab + (size_t)lane * kValuRecWords;
+  asm volatile("" : "+v"(lane_base));
+  if constexpr (G != kValuGroupConsensus) {
+#pragma unroll 1
+    for (int set = 0; set < kValuSets; ++set) {
+      const uint32_t* rec =
+          lane_base + (size_t)((OP * kValuSets + set) * 64) * kValuRecWords;
+      const volatile u32x4* p = (const volatile u32x4*)rec;  // 32-byte records
+      const u32x4 ab = p[0], ce = p[1];
+      const uint64_t a = valu_dpack(ab[0], ab[1]), b = valu_dpack(ab[2], ab[3]),
+                     c = valu_dpack(ce[0], ce[1]);
+      // test hook: flips bit 0 of the *expected* value
+      const uint64_t want = valu_dpack(ce[2], ce[3]) ^ (uint64_t)((pm >> G) & 1u);
+      const uint64_t got = valu_eval<KIND, IMM>(a, b, c);
+      ++w.count[G];
+      if (got != want) {
+        w.fail |= 1u << G;
+        valu_mismatch(L.ctl, L.records, w.key, w.simd, G, OP, set, lane, rep, want, got);
+      }
+    }
+  } else {
+    // every lane runs all inputs, from a rotation of its own; the digest is
+    // an order-independent sum, so all 64 lanes must end with the same value
+    uint64_t digest = 0;
+#pragma unroll 1
+    for (int i = 0; i < kValuConsInputs; ++i) {
+      const int idx = (i + 5 * lane) & (kValuConsInputs - 1);
+      const uint32_t* rec =
+          L.tab + (size_t)(OP * kValuSets * 64 + idx) * kValuRecWords;
+      asm volatile("" : "+v"(rec));
+      const u32x4 ab = *(const volatile u32x4*)rec;
+      const uint64_t a = valu_dpack(ab[0], ab[1]), b = valu_dpack(ab[2], ab[3]);
+      digest += valu_digest_term((uint32_t)OP, (uint32_t)idx,
+                                 valu_eval<KIND, IMM>(a, b, 0));
+      ++w.count[G];
+    }
+    const uint64_t first =
+        valu_dpack((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)digest),
+                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(digest >> 32)));
+    if (digest != first) {
+      w.fail |= 1u << G;
+      valu_mismatch(L.ctl, L.records, w.key, w.simd, G, OP, 0, lane, rep, first, digest);
+    }
+    w.digest[OP - kValuExactOps] = digest;
+  }
+#endif
+}
+static_assert((kValuConsInputs & (kValuConsInputs - 1)) == 0, "valu_step: rotation mask");
+
+template <int... OPS>
+__device__ __forceinline__ void valu_all_ops(std::integer_sequence<int, OPS...>,
+                                             const ValuLaunch& L, int lane, int rep,
+                                             unsigned pm, ValuWave& w) {
+  (valu_step<OPS>(L, lane, rep, pm, w), ...);
+}
+
+__global__ void __launch_bounds__(kCovBlock, kCovBlocksPerCu)
+valu_coverage_kernel(ValuLaunch L) {
+#if defined(__gfx950__)
+  __shared__ uint32_t lds[kCovLdsWords];  // the claim that keeps 2 per CU
+  const uint32_t hw_id = __builtin_amdgcn_s_getreg(kCovHwRegHwId);
+  const uint32_t xcc_id = __builtin_amdgcn_s_getreg(kCovHwRegXccId);
+  ValuWave w = {};
+  w.key = ((xcc_id & 0xFu) << 8) | ((hw_id >> 8) & 0xFFu);
+  w.simd = (hw_id >> 4) & 3u;
+  const unsigned pm =
+      (L.poison_all || (int)w.key == L.poison_key) ? L.poison_mask : 0u;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+#pragma unroll 1
+  for (int rep = 0; rep < L.reps; ++rep)
+    valu_all_ops(std::make_integer_sequence<int, kValuOps>{}, L, lane, rep, pm, w);
+
+  // the masks pass through LDS once (neighbouring lanes swap theirs), which
+  // keeps the static claim alive; the wave-wide OR below makes it a no-op
+  lds[tid * 64] = w.fail;  // tid < 256: index < kCovLdsWords
+  __syncthreads();
+  w.fail |= lds[(tid ^ 1) * 64];
+
+  // counted, not trusted: the wave's compares per group, summed by lane
+  // shuffles, added once to the global counters
+#pragma unroll
+  for (int g = 0; g < kValuGroups; ++g) {
+    uint32_t n = w.count[g];
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if (lane == 0) atomicAdd((unsigned long long*)&L.ctl[g], (unsigned long long)n);
+  }
+
+  unsigned wave_fail = 0;
+  for (int b = 0; b < kValuGroups; ++b)
+    if (__ballot((w.fail >> b) & 1u) != 0) wave_fail |= 1u << b;
+  if (lane == 0) {
+    const uint32_t slot = w.key * 4u + w.simd;  // < kCovSlots by the masks above
+    atomicAdd(&L.slots[slot], 1u);
+    if (wave_fail) atomicOr(&L.slots[kCovSlots + slot], wave_fail);
+    L.slots[2 * kCovSlots + slot] = hw_id;
+    L.slots[3 * kCovSlots + slot] = xcc_id;
+    // [round][block][wave]: round < max_rounds, block < gridDim.x, wave < 4,
+    // which is how the host sized the array
+    uint64_t* wr = L.wave_recs +
+                   ((size_t)(L.round * gridDim.x + blockIdx.x) * (kCovBlock / 64) +
+                    (tid >> 6)) * kValuWaveRecWords;
+    wr[0] = slot + 1u;
+    // test hook: bit 6 flips bit 0 of the digests this unit *reports*
+#pragma unroll
+    for (int i = 0; i < kValuConsOps; ++i)
+      wr[1 + i] = w.digest[i] ^ (uint64_t)((pm >> kValuGroupConsensus) & 1u);
+  }
+#endif
+}
+
+template <int OP>
+__device__ __forceinline__ void valu_probe_one(int op, uint64_t a, uint64_t b,
+                                               uint64_t c, uint64_t& r) {
+  if (op == OP) r = valu_eval<kValuOpKind[OP], kValuOpImm[OP]>(a, b, c);  // uniform
+}
+template <int... OPS>
+__device__ __forceinline__ void valu_probe_all(std::integer_sequence<int, OPS...>,
+                                               int op, uint64_t a, uint64_t b,
+                                               uint64_t c, uint64_t& r) {
+  (valu_probe_one<OPS>(op, a, b, c, r), ...);
+}
+
+// one wave, one op: in[0..63] a, in[64..127] b, in[128..191] c
+__global__ void __launch_bounds__(64, 1)
+valu_probe_kernel(int op, const uint64_t* __restrict__ in, uint64_t* __restrict__ out) {
+#if defined(__gfx950__)
+  const int lane = threadIdx.x;  // < 64
+  uint64_t r = 0;
+  valu_probe_all(std::make_integer_sequence<int, kValuOps>{}, op, in[lane],
+                 in[64 + lane], in[128 + lane], r);
+  out[lane] = r;
+#endif
+}
+
+static py::dict valu_reference() {
+  // host only: no HIP call
+  py::dict out;
+  out["sets"] = kValuSets;
+  out["lanes"] = 64;
+  py::list groups, items, ops;
+  for (int g = 0; g < kValuGroups; ++g) {
+    groups.append(kValuGroupNames[g]);
+    items.append(valu_items(g));
+  }
+  for (int op = 0; op < kValuOps; ++op) {
+    const ValuProblem p = valu_problem(op);
+    py::dict e;
+    e["name"] = kValuOpTable[op].name;
+    e["group"] = kValuGroupNames[kValuOpGroup[op]];
+    e["a"] = p.a;
+    e["b"] = p.b;
+    e["c"] = p.c;
+    if (p.expected.empty())
+      e["expected"] = py::none();
+    else
+      e["expected"] = p.expected;
+    ops.append(e);
+  }
+  out["groups"] = groups;
+  out["items"] = items;
+  out["ops"] = ops;
+  out["consensus_inputs"] = kValuConsInputs;
+  return out;
+}
+
+static std::vector<uint64_t> valu_probe(int device, const std::string& op_name,
+                                        const std::vector<uint64_t>& a,
+                                        const std::vector<uint64_t>& b,
+                                        const std::vector<uint64_t>& c) {
+  // everything is validated on the host before the first HIP call
+  const int op = valu_op_index(op_name);
+  if (a.size() != 64 || b.size() != 64 || c.size() != 64)
+    throw std::invalid_argument("valu_probe: a, b and c take 64 lanes each");
+  if (kValuOpGroup[op] == kValuGroupConsensus) {
+    for (int l = 0; l < 64; ++l)
+      valu_check_consensus_operand(kValuOpKind[op], a[l], b[l]);
+  } else {
+    std::vector<uint64_t> ref(64);
+    try {
+      valu_ref_wave(op, a.data(), b.data(), c.data(), ref.data());
+    } catch (const std::domain_error& e) {
+      throw std::invalid_argument(std::string("valu_probe: ") + e.what());
+    }
+  }
+  std::vector<uint64_t> in(192), out(64);
+  std::copy(a.begin(), a.end(), in.begin());
+  std::copy(b.begin(), b.end(), in.begin() + 64);
+  std::copy(c.begin(), c.end(), in.begin() + 128);
+  HIP_CHECK(hipSetDevice(device));
+  DeviceBuf<uint64_t> d_in(in.size()), d_out(out.size());
+  d_in.upload(in.data(), in.size());
+  d_out.fill(0);
+  hipLaunchKernelGGL(valu_probe_kernel, dim3(1), dim3(64), 0, 0, op, d_in.get(),
+                     d_out.get());
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
+  d_out.download(out.data(), out.size());
+  return out;
+}
+
+static py::dict valu_coverage_check(int device, int reps, int max_rounds,
+                                    int poison_key, unsigned poison_mask,
+                                    bool poison_all) {
+  if (poison_all && ((poison_mask >> kValuGroupConsensus) & 1u))
+    throw std::invalid_argument(
+        "valu_coverage_check: poison_all with the consensus bit cannot be "
+        "detected: a consensus poisoned everywhere is still a consensus");
+  DeviceBuf<uint64_t> d_ctl, d_wave;
+  DeviceBuf<ValuRecord> d_rec;
+  int round = 0, blocks = 0;
+  py::dict out = cov_run_sweep(
+      "valu_coverage_check", device, reps, max_rounds, poison_key, poison_mask,
+      kValuGroups, valu_build_table(),
+      [&](int cus, uint32_t* tab, uint32_t* slots) {
+        ValuLaunch L;
+        L.tab = tab, L.slots = slots, L.ctl = d_ctl.get(), L.records = d_rec.get();
+        L.wave_recs = d_wave.get();
+        L.reps = reps, L.poison_key = poison_key, L.poison_all = poison_all ? 1 : 0;
+        L.round = round++;  // < max_rounds: cov_run_sweep launches no more
+        L.poison_mask = poison_mask;
+        hipLaunchKernelGGL(valu_coverage_kernel, dim3(kCovBlocksPerCu * cus),
+                           dim3(kCovBlock), 0, 0, L);
+      },
+      [&](int cus) {
+        blocks = kCovBlocksPerCu * cus;
+        d_ctl = DeviceBuf<uint64_t>(kValuCtlWords);
+        d_rec = DeviceBuf<ValuRecord>(kValuMaxRecords);
+        d_wave = DeviceBuf<uint64_t>((size_t)max_rounds * blocks * (kCovBlock / 64) *
+                                     kValuWaveRecWords);
+        d_ctl.fill(0);
+        d_rec.fill(0);
+        d_wave.fill(0);
+      });
+
+  std::vector<uint64_t> ctl(kValuCtlWords), wave(d_wave.size());
+  std::vector<ValuRecord> rec(kValuMaxRecords);
+  d_ctl.download(ctl.data(), ctl.size());
+  d_rec.download(rec.data(), rec.size());
+  d_wave.download(wave.data(), wave.size());
+
+  // per slot, the distinct digest tuples its waves reported
+  std::vector<std::vector<std::vector<uint64_t>>> by_slot(kCovSlots);
+  const size_t n_wave = (size_t)round * blocks * (kCovBlock / 64);
+  for (size_t i = 0; i < n_wave; ++i) {
+    const uint64_t* wr = &wave[i * kValuWaveRecWords];
+    if (wr[0] == 0 || wr[0] > (uint64_t)kCovSlots) continue;
+    std::vector<uint64_t> tuple(wr + 1, wr + kValuWaveRecWords);
+    auto& seen = by_slot[wr[0] - 1];
+    if (std::find(seen.begin(), seen.end(), tuple) == seen.end()) seen.push_back(tuple);
+  }
+  py::list units;
+  for (py::handle h : out["units"]) {
+    py::dict u = py::reinterpret_borrow<py::dict>(h);
+    const int slot = u["key"].cast<int>() * 4 + u["simd"].cast<int>();
+    u["digests"] = by_slot[slot];
+    units.append(u);
+  }
+  out["units"] = units;
+
+  py::list compared, items, cons_ops, records;
+  for (int g = 0; g < kValuGroups; ++g) {
+    compared.append(ctl[g]);
+    items.append(valu_items(g));
+  }
+  for (int op = kValuExactOps; op < kValuOps; ++op) cons_ops.append(kValuOpTable[op].name);
+  const uint64_t errors = ctl[kValuCtlErrors];
+  const uint64_t kept = std::min<uint64_t>(errors, kValuMaxRecords);
+  for (uint64_t i = 0; i < kept; ++i) {
+    const ValuRecord& r = rec[i];
+    py::dict e;
+    e["key"] = r.key;
+    e["simd"] = r.simd;
+    e["group"] = r.group < (uint32_t)kValuGroups ? kValuGroupNames[r.group] : "?";
+    e["op"] = r.op < (uint32_t)kValuOps ? kValuOpTable[r.op].name : "?";
+    e["set"] = r.set;
+    e["lane"] = r.lane;
+    e["rep"] = r.rep;
+    e["expected"] = r.expected;
+    e["got"] = r.got;
+    records.append(e);
+  }
+  out["reps"] = reps;
+  out["compared"] = compared;
+  out["items"] = items;
+  out["consensus_ops"] = cons_ops;
+  out["records"] = records;
+  out["records_dropped"] = errors - kept;
+  out["error_count"] = errors;
+  return out;
+}
+
 
 PYBIND11_MODULE(_gpu_validator, m) {
   m.doc() = "MI355X (gfx950) native GPU health validator";
+  m.def("valu_coverage_check", &valu_coverage_check, py::arg("device") = 0,
+        py::arg("reps") = 4, py::arg("max_rounds") = 8,
+        py::arg("poison_key") = -1, py::arg("poison_mask") = 0u,
+        py::arg("poison_all") = false,
+        "Whole-device vector-ALU sweep: arithmetic, conversions and cross-lane "
+        "ops bit-exact, transcendentals by consensus, compares counted, per "
+        "(XCC, CU, SIMD)");
+  m.def("valu_reference", &valu_reference,
+        "Host-only: operands, expected words, items and op names of the "
+        "vector-ALU sweep");
+  m.def("valu_probe", &valu_probe, py::arg("device"), py::arg("op"), py::arg("a"),
+        py::arg("b"), py::arg("c"),
+        "Run one op of the vector-ALU table on one wave over the caller's "
+        "64-lane operands; returns the 64 raw results");
   m.def("host_link_check", &host_link_check, py::arg("device") = 0,
         py::arg("nbytes") = 64ull << 20, py::arg("seed") = 1ull,
         py::arg("kinds") =

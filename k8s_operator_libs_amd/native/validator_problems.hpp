@@ -6,8 +6,8 @@
 // tests/native/validator_problems_selftest.cpp drives all of it stand-alone
 // under AddressSanitizer + UBSan.  The functions the kernels call as well are
 // marked VALIDATOR_HD.  The generators of the LDS data-integrity check are in
-// lds_problems.hpp and those of the host-link check in hostlink_problems.hpp,
-// both included at the end.
+// lds_problems.hpp, those of the host-link check in hostlink_problems.hpp and
+// those of the vector-ALU check in valu_problems.hpp, all included at the end.
 
 #pragma once
 
@@ -743,3 +743,9 @@ inline XfAtomExpected xf_atom_expected(uint64_t seed, uint64_t threads, int reps
 // ---------------------------------------------------------------------------
 
 #include "hostlink_problems.hpp"
+
+// ---------------------------------------------------------------------------
+// Vector-ALU check: likewise.
+// ---------------------------------------------------------------------------
+
+#include "valu_problems.hpp"

@@ -39,7 +39,12 @@ Layers:
   in both directions, zero-copy kernel access, duplex and unaligned copies on
   pinned, registered and pageable host memory and system-scope atomics on
   pinned memory, exact, coverage counted, failing words and copy cases
-  recorded (:func:`summarize_host_link` is the pure verdict).
+  recorded (:func:`summarize_host_link` is the pure verdict);
+- :func:`valu_check` — opt-in whole-device sweep of the vector ALU: f32 / f64 /
+  f16 arithmetic, integer and bit ops, conversions (f16, bf16, fp8, bf8, fp4)
+  and cross-lane ops bit-exact against a host reference, raw transcendentals
+  by consensus of all SIMDs, every compare counted, failures attributed per
+  unit and instruction (:func:`summarize_valu` is the pure verdict).
 """
 
 from .gpu_health import (  # noqa: F401
@@ -67,6 +72,10 @@ from .lds_integrity import (  # noqa: F401
 from .mx_matrix import (  # noqa: F401
     mx_matrix_check,
     summarize_mx_matrix,
+)
+from .valu_check import (  # noqa: F401
+    summarize_valu,
+    valu_check,
 )
 from .xcd_fabric import (  # noqa: F401
     summarize_xcd_fabric,

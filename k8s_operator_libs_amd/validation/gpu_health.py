@@ -95,6 +95,7 @@ def gpu_health_check(
     lds: bool = False,
     hostlink: bool = False,
     hostlink_mib: float = 64.0,
+    valu: bool = False,
 ) -> Dict[str, Any]:
     """Full node GPU health check.  Returns a report dict with a top-level
     ``healthy`` verdict; raises GpuHealthError when ``require_gpu`` and no
@@ -111,7 +112,9 @@ def gpu_health_check(
     it.  ``hostlink`` adds the host-link data-integrity check with
     ``hostlink_mib`` MiB per buffer (DMA copies, zero-copy access and
     system-scope atomics on host memory; see :mod:`.host_link`) and gates on it
-    as well."""
+    as well.  ``valu`` adds the whole-device vector-ALU sweep (exact
+    arithmetic, conversions and cross-lane ops, transcendentals by consensus;
+    see :mod:`.valu_check`) and gates on it."""
     report: Dict[str, Any] = {"healthy": False, "checks": {}}
     report["checks"]["smi"] = smi_probe()
 
@@ -222,6 +225,16 @@ def gpu_health_check(
         report["checks"]["host_link"] = link
         host_link_ok = link["healthy"]
 
+    valu_ok = True
+    if valu:
+        # opt-in: the vector ALU on every CU and SIMD, summary without raw
+        # units or records
+        from .valu_check import summarize_valu
+
+        valu_summary = summarize_valu(native.valu_coverage_check(device))
+        report["checks"]["valu"] = valu_summary
+        valu_ok = valu_summary["healthy"]
+
     # multi-GPU nodes: verify every xGMI peer link is up
     xgmi_ok = True
     if probe.get("device_count", 1) > 1:
@@ -244,6 +257,7 @@ def gpu_health_check(
         and fabric_ok
         and lds_integrity_ok
         and host_link_ok
+        and valu_ok
     )
     return report
 
@@ -256,7 +270,8 @@ def main() -> int:
     block-scaled matrix sweep and burn-in, ``--fabric`` for the cross-XCD
     hand-off and atomics check, ``--lds`` for the LDS data-integrity check and
     ``--hostlink`` for the host-link data-integrity check (``--hostlink-mib=N``
-    sets its buffer size and implies it)."""
+    sets its buffer size and implies it) and ``--valu`` for the vector-ALU
+    sweep."""
     import sys
 
     sized_kw: Dict[str, Any] = {}
@@ -278,6 +293,7 @@ def main() -> int:
         mx="--mx" in sys.argv,
         fabric="--fabric" in sys.argv,
         lds="--lds" in sys.argv,
+        valu="--valu" in sys.argv,
         **sized_kw,
     )
     print(json.dumps(report, indent=2, default=str))  # noqa: T201 (CLI/build output)
