@@ -13,14 +13,6 @@ import sysconfig
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SOURCE = os.path.join(PKG_DIR, "gpu_validator.hip")
-SOURCES = (
-    SOURCE,
-    os.path.join(PKG_DIR, "hip_util.hpp"),
-    os.path.join(PKG_DIR, "validator_problems.hpp"),
-    os.path.join(PKG_DIR, "lds_problems.hpp"),
-    os.path.join(PKG_DIR, "hostlink_problems.hpp"),
-    os.path.join(PKG_DIR, "valu_problems.hpp"),
-)
 OUTPUT = os.path.join(PKG_DIR, "_gpu_validator.so")
 JSONOPS_SOURCE = os.path.join(PKG_DIR, "jsonops.cpp")
 JSONOPS_OUTPUT = os.path.join(PKG_DIR, "_jsonops.so")
@@ -35,10 +27,20 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 
 
+def validator_sources() -> list:
+    """gpu_validator.hip and its headers: every ``*.hpp`` next to it except
+    the two ``wire_*.hpp`` that belong to ``_wire.so``."""
+    wire = {os.path.basename(p) for p in WIRE_SOURCES}
+    return [SOURCE] + sorted(
+        os.path.join(PKG_DIR, name) for name in os.listdir(PKG_DIR)
+        if name.endswith(".hpp") and name not in wire)
+
+
 def is_built() -> bool:
     """Stale when gpu_validator.hip or one of its headers is newer than the .so."""
     return os.path.exists(OUTPUT) and all(
-        os.path.getmtime(OUTPUT) >= os.path.getmtime(src) for src in SOURCES)
+        os.path.getmtime(OUTPUT) >= os.path.getmtime(src)
+        for src in validator_sources())
 
 
 def build_jsonops(force: bool = False, verbose: bool = False) -> str:

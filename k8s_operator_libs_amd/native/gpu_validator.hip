@@ -52,6 +52,9 @@
 // This file holds the kernels, the HIP host drivers, the py::dict conversion
 // and the module table.  Device memory and events are owned by the holders in
 // hip_util.hpp (DeviceBuf<T>, HostBuf, RegisteredBuf, Stream, EventTimer);
+// the capped mismatch log of the checks is record_log.hpp, the bounded
+// relaunch of a whole-device sweep and its unit dicts are sweep.hpp, and the
+// tally of what a launch left behind is plain C++ next to the problems;
 // the exact problems the checks run (operands, codecs, packed tables, expected results, and the records and
 // constants shared with the kernels) are plain C++ in validator_problems.hpp.
 //
@@ -75,6 +78,8 @@
 #include <vector>
 
 #include "hip_util.hpp"
+#include "record_log.hpp"
+#include "sweep.hpp"
 #include "validator_problems.hpp"
 
 namespace py = pybind11;
@@ -467,17 +472,8 @@ static py::list xgmi_p2p_probe(int device, double buf_mib, int iters) {
 // makes one round the normal case; the host relaunches (bounded) otherwise.
 // ---------------------------------------------------------------------------
 
-constexpr int kCovLdsWords = 16384;         // 64 KiB static LDS per workgroup
-constexpr int kCovKeys = 4096;              // 4 XCC bits + 8 HW_ID bits
-constexpr int kCovSlots = kCovKeys * 4;     // x 4 SIMDs
-constexpr int kCovBlock = 256;              // one wave per SIMD, normally
-constexpr int kCovBlocksPerCu = 2;          // floor(160 KiB / 64 KiB)
 constexpr unsigned kCovFailF32 = 1u, kCovFailBf16 = 2u, kCovFailFp8 = 4u,
                    kCovFailLds = 8u;
-
-// s_getreg simm16 = id | offset << 6 | (size - 1) << 11; full 32 bits of each.
-constexpr int kCovHwRegHwId = 4 | (31 << 11);
-constexpr int kCovHwRegXccId = 20 | (31 << 11);
 
 using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 
@@ -587,121 +583,32 @@ static py::dict cu_coverage_reference() {
   return out;
 }
 
-// The host side of a whole-device sweep, shared by cu_coverage_check and
-// mx_coverage_check: argument validation before the first HIP call, table
-// upload, bounded relaunch until every CU and SIMD has been seen, and the
-// per-slot result table.  `launch(cus, tab, slots)` enqueues one round of the
-// sweep's kernel on a grid of kCovBlocksPerCu x CUs workgroups.  A sweep with
-// buffers of its own sized by the CU count allocates them in `prepare(cus)`,
-// which runs once, after the device is selected and before the first launch.
-template <typename Launch, typename Prepare>
-static py::dict cov_run_sweep(const std::string& who, int device, int reps,
-                              int max_rounds, int poison_key,
-                              unsigned poison_mask, int mask_bits,
-                              const std::vector<uint32_t>& tab, Launch launch,
-                              Prepare prepare) {
-  if (reps < 1 || reps > 4096)
-    throw std::invalid_argument(who + ": reps must be in [1, 4096]");
-  if (max_rounds < 1 || max_rounds > 64)
-    throw std::invalid_argument(who + ": max_rounds must be in [1, 64]");
-  if (poison_key < -1 || poison_key >= kCovKeys)
-    throw std::invalid_argument(who + ": poison_key out of range");
-  if (poison_mask >= (1u << mask_bits))
-    throw std::invalid_argument(who + ": poison_mask has " +
-                                std::to_string(mask_bits) + " bits");
-
-  hipDeviceProp_t prop;
-  HIP_CHECK(hipSetDevice(device));
-  HIP_CHECK(hipGetDeviceProperties(&prop, device));
-  const int cus = prop.multiProcessorCount;
-  if (cus < 1 || cus > kCovKeys)
-    throw std::runtime_error(who + ": implausible compute unit count");
-  if (prop.sharedMemPerBlock < sizeof(uint32_t) * kCovLdsWords)
-    throw std::runtime_error(
-        who + ": device grants less than 64 KiB of LDS per workgroup");
-
-  DeviceBuf<uint32_t> d_tab(tab.size());
-  DeviceBuf<uint32_t> d_slots((size_t)4 * kCovSlots);  // waves | fail | hw_id | xcc_id
-  d_tab.upload(tab.data(), tab.size());
-  d_slots.fill(0);
-  prepare(cus);
-  EventTimer timer;
-
-  std::vector<uint32_t> h(d_slots.size());
-  const uint32_t* h_waves = h.data();
-  const uint32_t* h_fail = h.data() + kCovSlots;
-  const uint32_t* h_hw = h.data() + 2 * kCovSlots;
-  const uint32_t* h_xcc = h.data() + 3 * kCovSlots;
-  int rounds = 0, cus_covered = 0, slots_covered = 0;
-  double elapsed_ms = 0.0;
-  while (rounds < max_rounds) {
-    elapsed_ms += timer.time_ms([&] {
-      launch(cus, d_tab.get(), d_slots.get());
-      HIP_CHECK(hipGetLastError());
-    });
-    ++rounds;
-    d_slots.download(h.data(), h.size());
-    cus_covered = slots_covered = 0;
-    for (int key = 0; key < kCovKeys; ++key) {
-      int simds = 0;
-      for (int s = 0; s < 4; ++s) simds += h_waves[key * 4 + s] != 0;
-      cus_covered += simds != 0;
-      slots_covered += simds;
-    }
-    if (cus_covered >= cus && slots_covered >= 4 * cus) break;
-  }
-
-  py::list units;
-  long waves_run = 0;
-  int failed_slots = 0;
-  for (int slot = 0; slot < kCovSlots; ++slot) {
-    if (h_waves[slot] == 0) continue;
-    const int key = slot >> 2;
-    py::dict u;
-    u["key"] = key;
-    u["xcc"] = key >> 8;
-    u["hw_bits"] = key & 0xFF;
-    u["simd"] = slot & 3;
-    u["waves"] = h_waves[slot];
-    u["fail_mask"] = h_fail[slot];
-    u["hw_id_raw"] = h_hw[slot];
-    u["xcc_id_raw"] = h_xcc[slot];
-    units.append(u);
-    waves_run += h_waves[slot];
-    failed_slots += h_fail[slot] != 0;
-  }
-  py::dict out;
-  out["compute_units"] = cus;
-  out["cus_covered"] = cus_covered;
-  out["simd_slots_covered"] = slots_covered;
-  out["waves_run"] = waves_run;
-  out["rounds"] = rounds;
-  out["failed_slots"] = failed_slots;
-  out["units"] = units;
-  out["elapsed_ms"] = elapsed_ms;
-  return out;
-}
-
-template <typename Launch>
-static py::dict cov_run_sweep(const std::string& who, int device, int reps,
-                              int max_rounds, int poison_key,
-                              unsigned poison_mask, int mask_bits,
-                              const std::vector<uint32_t>& tab, Launch launch) {
-  return cov_run_sweep(who, device, reps, max_rounds, poison_key, poison_mask,
-                       mask_bits, tab, launch, [](int) {});
+// The host side of cu_coverage_check and mx_coverage_check, whose kernels take
+// the same arguments: validation before the first HIP call, then the sweep.
+using CovSweepKernel = void (*)(const uint32_t*, uint32_t*, uint32_t*, uint32_t*,
+                                uint32_t*, int, int, unsigned, int);
+static py::dict cov_sweep_check(const std::string& who, CovSweepKernel kernel,
+                                int mask_bits, const std::vector<uint32_t>& tab,
+                                int device, int reps, int max_rounds,
+                                int poison_key, unsigned poison_mask,
+                                bool poison_all) {
+  cov_validate(who, reps, max_rounds, poison_key, poison_mask, mask_bits);
+  const int cus = cov_select_device(who, device);
+  return cov_sweep_dict(cov_run_sweep(
+      cus, max_rounds, tab, [&](int, uint32_t* d_tab, uint32_t* slots) {
+        hipLaunchKernelGGL(kernel, dim3(kCovBlocksPerCu * cus), dim3(kCovBlock), 0,
+                           0, d_tab, slots, slots + kCovSlots, slots + 2 * kCovSlots,
+                           slots + 3 * kCovSlots, reps, poison_key, poison_mask,
+                           poison_all ? 1 : 0);
+      }));
 }
 
 static py::dict cu_coverage_check(int device, int reps, int max_rounds,
                                   int poison_key, unsigned poison_mask,
                                   bool poison_all) {
-  return cov_run_sweep(
-      "cu_coverage_check", device, reps, max_rounds, poison_key, poison_mask, 4,
-      cov_build_table(), [&](int cus, uint32_t* tab, uint32_t* slots) {
-        hipLaunchKernelGGL(cu_coverage_kernel, dim3(kCovBlocksPerCu * cus),
-                           dim3(kCovBlock), 0, 0, tab, slots, slots + kCovSlots,
-                           slots + 2 * kCovSlots, slots + 3 * kCovSlots, reps,
-                           poison_key, poison_mask, poison_all ? 1 : 0);
-      });
+  return cov_sweep_check("cu_coverage_check", cu_coverage_kernel, 4,
+                         cov_build_table(), device, reps, max_rounds, poison_key,
+                         poison_mask, poison_all);
 }
 
 // ---------------------------------------------------------------------------
@@ -988,15 +895,9 @@ mx_coverage_kernel(const uint32_t* tab, uint32_t* __restrict__ slot_waves,
 static py::dict mx_coverage_check(int device, int reps, int max_rounds,
                                   int poison_key, unsigned poison_mask,
                                   bool poison_all) {
-  return cov_run_sweep(
-      "mx_coverage_check", device, reps, max_rounds, poison_key, poison_mask,
-      kMxFailBits, mx_build_table(),
-      [&](int cus, uint32_t* tab, uint32_t* slots) {
-        hipLaunchKernelGGL(mx_coverage_kernel, dim3(kCovBlocksPerCu * cus),
-                           dim3(kCovBlock), 0, 0, tab, slots, slots + kCovSlots,
-                           slots + 2 * kCovSlots, slots + 3 * kCovSlots, reps,
-                           poison_key, poison_mask, poison_all ? 1 : 0);
-      });
+  return cov_sweep_check("mx_coverage_check", mx_coverage_kernel, kMxFailBits,
+                         mx_build_table(), device, reps, max_rounds, poison_key,
+                         poison_mask, poison_all);
 }
 
 // MX burn-in: the analogue of mfma_burn_kernel on 16x16x128, e2m1 or e4m3,
@@ -1141,11 +1042,9 @@ __device__ __forceinline__ void hbm_report(const HbmLaunch& a, uint64_t i,
   if (x == 0) return;
   ++bad;
   bad_xor |= x;
-  const unsigned long long slot = atomicAdd(&a.ctl[kHbmCtlClaims], 1ull);
-  if (slot < a.max_records) {  // claims past the cap are dropped
-    HbmRecord r = {i, a.verify_index, got ^ x, got};
-    a.records[slot] = r;
-  }
+  record_log_claim(
+      RecordLogView<HbmRecord>{&a.ctl[kHbmCtlClaims], a.records, a.max_records},
+      [&] { return HbmRecord{i, a.verify_index, got ^ x, got}; });
 }
 
 // kind: kHbmFill / kHbmVerifyInvert / kHbmVerify.  16-byte nontemporal
@@ -1267,6 +1166,33 @@ static std::vector<uint64_t> hbm_pattern_reference(const std::string& pattern,
   return out;
 }
 
+// The result tables of hbm_pattern_kernel and of the host-link kernels built
+// like it: the control block with the record log, and the sharded counters.
+struct HbmTables {
+  RecordLog<HbmRecord> log;
+  DeviceBuf<unsigned long long> shards{(size_t)kHbmShards * kHbmShardStride};
+  explicit HbmTables(int max_records)
+      : log((size_t)std::max(1, max_records), kHbmCtlWords, kHbmCtlClaims) {
+    shards.fill(0);
+  }
+  void attach(HbmLaunch& a, size_t cap) const {
+    const RecordLogView<HbmRecord> v = log.view(cap);
+    a.ctl = log.ctl();
+    a.shards = shards.get();
+    a.records = v.records;
+    a.max_records = v.cap;
+  }
+  // after a synchronise: the words the kernels counted; `rezero` for a next phase
+  uint64_t words_compared(bool rezero = false) {
+    std::vector<unsigned long long> sh(shards.size());
+    shards.download(sh.data(), sh.size());
+    uint64_t n = 0;
+    for (int s = 0; s < kHbmShards; ++s) n += sh[(size_t)s * kHbmShardStride];
+    if (rezero) shards.fill(0);
+    return n;
+  }
+};
+
 struct HbmChunk {
   DeviceBuf<uint64_t> buf;
   uint64_t first_word = 0;  // logical
@@ -1297,10 +1223,8 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
   if (chunk_bytes == 0 || chunk_bytes % 8 != 0)
     throw std::invalid_argument(
         "hbm_pattern_check: chunk_bytes must be a positive multiple of 8");
-  if (passes < 1 || passes > kHbmMaxPasses)
-    throw std::invalid_argument("hbm_pattern_check: passes must be in [1, 16]");
-  if (max_records < 1 || max_records > kHbmMaxRecords)
-    throw std::invalid_argument("hbm_pattern_check: max_records must be in [1, 4096]");
+  require_range("hbm_pattern_check", "passes", passes, 1, kHbmMaxPasses);
+  require_range("hbm_pattern_check", "max_records", max_records, 1, kHbmMaxRecords);
   if (first_word > (1ull << 62) || nbytes > (1ull << 62))
     throw std::invalid_argument("hbm_pattern_check: region out of the index range");
   const int n_patterns = passes + (checker ? 1 : 0);
@@ -1342,12 +1266,7 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
     c.buf = DeviceBuf<uint64_t>((size_t)c.words);
   }
 
-  DeviceBuf<unsigned long long> d_ctl(kHbmCtlWords);
-  DeviceBuf<unsigned long long> d_shards((size_t)kHbmShards * kHbmShardStride);
-  DeviceBuf<HbmRecord> d_records((size_t)max_records);
-  d_ctl.fill(0);
-  d_shards.fill(0);
-  d_records.fill(0);
+  HbmTables tables(max_records);
   EventTimer timer;
 
   static const char* const kKindNames[3] = {"fill", "verify_invert", "verify"};
@@ -1371,10 +1290,7 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
           a.poison_xor = poison_xor;
           a.poison_stride = poison_stride;
           a.poison_word = poisoned ? poison_word : -1;
-          a.ctl = d_ctl.get();
-          a.shards = d_shards.get();
-          a.records = d_records.get();
-          a.max_records = (uint32_t)max_records;
+          tables.attach(a, (size_t)max_records);
           a.verify_index = (uint32_t)verify_index;
           a.pattern = is_hash ? kHbmPatternHash : kHbmPatternChecker;
           hbm_launch(kind, a);
@@ -1398,17 +1314,8 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
     }
   }
 
-  unsigned long long ctl[kHbmCtlWords];
-  std::vector<unsigned long long> shards(d_shards.size());
-  d_ctl.download(ctl, kHbmCtlWords);
-  d_shards.download(shards.data(), shards.size());
-  const uint64_t claims = ctl[kHbmCtlClaims];
-  const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)max_records);
-  std::vector<HbmRecord> recs(kept);
-  if (kept) d_records.download(recs.data(), kept);
-  uint64_t words_verified = 0;
-  for (int s = 0; s < kHbmShards; ++s)
-    words_verified += shards[(size_t)s * kHbmShardStride];
+  const auto log = tables.log.collect((size_t)max_records);
+  const uint64_t words_verified = tables.words_compared();
 
   py::list chunk_list;
   for (size_t c = 0; c < chunks.size(); ++c) {
@@ -1419,7 +1326,7 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
     chunk_list.append(e);
   }
   py::list records;
-  for (const HbmRecord& r : recs) {
+  for (const HbmRecord& r : log.records) {
     py::dict e;
     e["word"] = r.word;
     e["byte_offset"] = 8 * (r.word - first_word);
@@ -1437,10 +1344,10 @@ static py::dict hbm_pattern_check(int device, uint64_t nbytes,
   out["phases"] = phases;
   out["words_verified"] = words_verified;
   out["words_expected"] = words * (uint64_t)n_verify;
-  out["error_count"] = ctl[kHbmCtlErrors];
-  out["xor_or"] = ctl[kHbmCtlXor];
+  out["error_count"] = log.ctl[kHbmCtlErrors];
+  out["xor_or"] = log.ctl[kHbmCtlXor];
   out["records"] = records;
-  out["records_dropped"] = claims - (uint64_t)kept;
+  out["records_dropped"] = log.claims - (uint64_t)log.records.size();
   out["elapsed_ms"] = elapsed_ms;
   out["beyond_cache"] = nbytes > kHbmBeyondCacheBytes;
   return out;
@@ -1562,12 +1469,11 @@ __device__ __forceinline__ void xf_report(const XfHandoff& a, uint32_t rep,
                                           uint32_t wx, uint32_t rx, uint32_t kind,
                                           uint32_t extra, uint64_t expected,
                                           uint64_t got) {
-  const unsigned long long slot = atomicAdd(&a.ctl[kXfCtlClaims], 1ull);
-  if (slot < a.max_records) {  // claims past the cap are dropped
-    XfRecord r = {a.round, rep, group, member, line, word, wx, rx, kind, extra,
-                  expected, got};
-    a.records[slot] = r;
-  }
+  const XfRecord r = {a.round, rep, group, member, line, word, wx, rx, kind, extra,
+                      expected, got};
+  record_log_claim(
+      RecordLogView<XfRecord>{&a.ctl[kXfCtlClaims], a.records, a.max_records},
+      [&] { return r; });
 }
 
 // All waves of a reducer compare every payload half of group `vg` at
@@ -1828,23 +1734,17 @@ struct XfShape {
 
 // every argument is validated here, before the first HIP call
 static void xf_validate(const std::string& who, const XfShape& s) {
-  if (s.reps < 1 || s.reps > 64)
-    throw std::invalid_argument(who + ": reps must be in [1, 64]");
-  if (s.group < 2 || s.group > 64)
-    throw std::invalid_argument(who + ": group must be in [2, 64]");
-  if (s.slab_lines < 1 || s.slab_lines > 32)
-    throw std::invalid_argument(who + ": slab_lines must be in [1, 32]");
-  if (s.cells < 1 || s.cells > 4096)
-    throw std::invalid_argument(who + ": cells must be in [1, 4096]");
+  require_range(who, "reps", s.reps, 1, 64);
+  require_range(who, "group", s.group, 2, 64);
+  require_range(who, "slab_lines", s.slab_lines, 1, 32);
+  require_range(who, "cells", s.cells, 1, 4096);
   if (s.blocks < 0 || s.blocks > kXfMaxBlocks ||
       (s.blocks > 0 && s.blocks % s.group != 0))
     throw std::invalid_argument(
         who + ": blocks must be 0 (derive from the device) or a positive "
               "multiple of group, at most 1024");
-  if (s.max_rounds < 2 || s.max_rounds > 64)
-    throw std::invalid_argument(who + ": max_rounds must be in [2, 64]");
-  if (s.max_records < 1 || s.max_records > kXfMaxRecords)
-    throw std::invalid_argument(who + ": max_records must be in [1, 4096]");
+  require_range(who, "max_rounds", s.max_rounds, 2, 64);
+  require_range(who, "max_records", s.max_records, 1, kXfMaxRecords);
   if (s.poison_mask >= (1u << kXfPoisonBits))
     throw std::invalid_argument(who + ": poison_mask has 9 bits");
   if (s.poison_pair < -1 || s.poison_pair > 0xFF)
@@ -1875,8 +1775,7 @@ static py::dict xcd_fabric_reference(int blocks, uint64_t seed, int reps,
   xf_validate("xcd_fabric_reference", s);
   if (blocks < 1)
     throw std::invalid_argument("xcd_fabric_reference: blocks must be given");
-  if (round < -1 || round >= 64)
-    throw std::invalid_argument("xcd_fabric_reference: round must be in [-1, 63]");
+  require_range("xcd_fabric_reference", "round", round, -1, 63);
   if (rep < 0 || rep >= reps || block < 0 || block >= blocks || line < 0 ||
       line >= slab_lines)
     throw std::invalid_argument(
@@ -2057,12 +1956,7 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
                      max_records, poison_mask, poison_pair};
   xf_validate("xcd_fabric_check", s);
 
-  hipDeviceProp_t prop;
-  HIP_CHECK(hipSetDevice(device));
-  HIP_CHECK(hipGetDeviceProperties(&prop, device));
-  const int cus = prop.multiProcessorCount;
-  if (cus < 1 || cus > kCovKeys)
-    throw std::runtime_error("xcd_fabric_check: implausible compute unit count");
+  const int cus = select_device("xcd_fabric_check", device).multiProcessorCount;
   // G: the largest odd number with group x G <= 2 x CUs (at least one group)
   int G = blocks > 0 ? blocks / group : (2 * cus) / group;
   if (blocks == 0) {
@@ -2086,13 +1980,11 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
   DeviceBuf<uint64_t> d_slab(slab_words);
   DeviceBuf<uint32_t> d_tickets(n_tickets * kXfTicketStride);
   DeviceBuf<uint32_t> d_writer(writer_count);
-  DeviceBuf<unsigned long long> d_ctl(kXfCtlWords), d_pair(kXfPairPlanes * kPlane);
-  DeviceBuf<XfRecord> d_records((size_t)max_records);
+  DeviceBuf<unsigned long long> d_pair(kXfPairPlanes * kPlane);
+  RecordLog<XfRecord> log((size_t)max_records, kXfCtlWords, kXfCtlClaims);
   d_slab.upload(h_slab.data(), slab_words);
   d_writer.fill(0xFF);
-  d_ctl.fill(0);
   d_pair.fill(0);
-  d_records.fill(0);
   EventTimer timer;
 
   std::vector<uint32_t> h_tickets(d_tickets.size());
@@ -2104,21 +1996,22 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
   unsigned xcc_mask = 0;
   double elapsed_ms = 0.0;
   py::list round_ms;
+  const RecordLogView<XfRecord> log_view = log.view((size_t)max_records);
   while (rounds < max_rounds) {
     XfHandoff a;
     a.slab = d_slab.get();
     a.tickets = d_tickets.get();
     a.writer_xcc = d_writer.get();
-    a.ctl = d_ctl.get();
+    a.ctl = log.ctl();
     a.pair = d_pair.get();
-    a.records = d_records.get();
+    a.records = log_view.records;
     a.seed = seed;
     a.round = (uint32_t)rounds;
     a.reps = (uint32_t)reps;
     a.group = (uint32_t)group;
     a.G = (uint32_t)G;
     a.slab_lines = (uint32_t)slab_lines;
-    a.max_records = (uint32_t)max_records;
+    a.max_records = log_view.cap;
     a.poison_mask = poison_mask;
     a.poison_pair = poison_pair;
     const float ms = timer.time_ms([&] {
@@ -2156,17 +2049,13 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
     if (rounds >= 2 && pairs_covered >= xcc_seen * xcc_seen) break;
   }
 
-  unsigned long long ctl[kXfCtlWords];
-  d_ctl.download(ctl, kXfCtlWords);
-  const uint64_t claims = ctl[kXfCtlClaims];
-  const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)max_records);
-  std::vector<XfRecord> recs(kept);
-  if (kept) d_records.download(recs.data(), kept);
+  const auto taken = log.collect((size_t)max_records);
+  const std::vector<unsigned long long>& ctl = taken.ctl;
 
   py::dict atomics = xf_run_atomics(cus, s, seed, elapsed_ms);
 
   py::list records;
-  for (const XfRecord& r : recs) {
+  for (const XfRecord& r : taken.records) {
     py::dict e;
     const bool payload = r.kind == kXfKindPayload;
     const uint64_t idx =
@@ -2249,7 +2138,7 @@ static py::dict xcd_fabric_check(int device, int reps, int group, int slab_lines
   out["xcc_ids"] = xcc_ids;
   out["writes_per_xcc"] = writes_per_xcc;
   out["records"] = records;
-  out["records_dropped"] = claims - (uint64_t)kept;
+  out["records_dropped"] = taken.claims - (uint64_t)taken.records.size();
   out["atomics"] = atomics;
   out["elapsed_ms"] = elapsed_ms;
   return out;
@@ -2326,11 +2215,10 @@ using s16x4 = __attribute__((ext_vector_type(4))) short;
 // (by value and out of line: the lane's counters stay in registers)
 __device__ __noinline__ void lds_record(unsigned long long* ctl, LdsRecord* records,
                                         uint32_t max_records, LdsRecord r) {
-  if (__hip_atomic_load(&ctl[kLdsCtlClaims], __ATOMIC_RELAXED,
-                        __HIP_MEMORY_SCOPE_AGENT) >= max_records)
-    return;
-  const unsigned long long slot = atomicAdd(&ctl[kLdsCtlClaims], 1ull);
-  if (slot < max_records) records[slot] = r;  // claims past the cap are dropped
+  const RecordLogView<LdsRecord> log = {&ctl[kLdsCtlClaims], records, max_records};
+  if (__hip_atomic_load(log.claims, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
+      log.cap)  // a full log is left alone: no atomic per further mismatch
+    record_log_claim(log, [&] { return r; });
 }
 
 __device__ __forceinline__ void lds_check(const LdsLaunch& a, LdsLane& st,
@@ -2786,17 +2674,13 @@ struct LdsShape {
 
 // every argument is validated here, before the first HIP call
 static void lds_validate(const std::string& who, const LdsShape& s) {
-  if (s.reps < 1 || s.reps > kLdsMaxReps)
-    throw std::invalid_argument(who + ": reps must be in [1, 4096]");
-  if (s.passes < 1 || s.passes > kLdsMaxPasses)
-    throw std::invalid_argument(who + ": passes must be in [1, 16]");
-  if (s.max_rounds < 1 || s.max_rounds > 64)
-    throw std::invalid_argument(who + ": max_rounds must be in [1, 64]");
+  require_range(who, "reps", s.reps, 1, kLdsMaxReps);
+  require_range(who, "passes", s.passes, 1, kLdsMaxPasses);
+  require_range(who, "max_rounds", s.max_rounds, 1, 64);
   if (s.blocks < 0 || s.blocks > kLdsMaxBlocks)
     throw std::invalid_argument(
         who + ": blocks must be 0 (two per compute unit) or in [1, 65536]");
-  if (s.poison_key < -1 || s.poison_key >= kCovKeys)
-    throw std::invalid_argument(who + ": poison_key out of range");
+  require_poison_key(who, s.poison_key);
   if (s.poison_mask >= (1u << kLdsPhases))
     throw std::invalid_argument(who + ": poison_mask has 6 bits");
   if (s.poison_word < -1 || s.poison_word >= kLdsWords)
@@ -2820,83 +2704,51 @@ static py::dict lds_integrity_check(int device, int reps, int passes,
                       poison_mask, poison_xor};
   lds_validate("lds_integrity_check", s);
 
-  hipDeviceProp_t prop;
-  HIP_CHECK(hipSetDevice(device));
-  HIP_CHECK(hipGetDeviceProperties(&prop, device));
-  const int cus = prop.multiProcessorCount;
-  if (cus < 1 || cus > kCovKeys)
-    throw std::runtime_error("lds_integrity_check: implausible compute unit count");
+  const int cus = select_device("lds_integrity_check", device).multiProcessorCount;
   const int grid = blocks > 0 ? blocks : kCovBlocksPerCu * cus;
 
   const std::vector<uint32_t> h_src = lds_dma_source(seed);
   DeviceBuf<uint32_t> d_src(h_src.size());
   DeviceBuf<uint32_t> d_keys((size_t)kLdsKeyPlanes * kCovKeys);
-  DeviceBuf<unsigned long long> d_ctl(kLdsCtlWords), d_counters(kLdsPhases);
-  DeviceBuf<LdsRecord> d_records(kLdsMaxRecords);
+  DeviceBuf<unsigned long long> d_counters(kLdsPhases);
+  RecordLog<LdsRecord> log(kLdsMaxRecords, kLdsCtlWords, kLdsCtlClaims);
   d_src.upload(h_src.data(), h_src.size());
   d_keys.fill(0);
-  d_ctl.fill(0);
   d_counters.fill(0);
-  d_records.fill(0);
-  EventTimer timer;
 
+  const RecordLogView<LdsRecord> log_view = log.view(kLdsMaxRecords);
   LdsLaunch a;
   a.src = d_src.get();
   a.keys = d_keys.get();
-  a.ctl = d_ctl.get();
+  a.ctl = log.ctl();
   a.counters = d_counters.get();
-  a.records = d_records.get();
+  a.records = log_view.records;
   a.seed = seed;
   a.reps = (uint32_t)reps;
   a.passes = (uint32_t)passes;
-  a.max_records = kLdsMaxRecords;
+  a.max_records = log_view.cap;
   a.poison_mask = poison_mask;
   a.poison_xor = (uint32_t)poison_xor;
   a.poison_key = poison_key;
   a.poison_all = poison_all ? 1 : 0;
   a.poison_word = poison_word;
 
-  std::vector<uint32_t> h(d_keys.size());
-  int rounds = 0, cus_covered = 0;
-  double elapsed_ms = 0.0;
-  while (rounds < max_rounds) {
-    // A device or partition that grants less than 160 KiB to a workgroup
-    // rejects the launch: that raises here, it never tests less.  The launch
-    // status decides, not the sharedMemPerBlock property.
-    elapsed_ms += timer.time_ms([&] {
-      hipLaunchKernelGGL(lds_integrity_kernel, dim3(grid), dim3(kLdsBlock), 0, 0, a);
-      HIP_CHECK(hipGetLastError());
-    });
-    ++rounds;
-    d_keys.download(h.data(), h.size());
-    cus_covered = 0;
-    for (int key = 0; key < kCovKeys; ++key) cus_covered += h[key] != 0;
-    if (cus_covered >= cus) break;
-  }
+  // A device or partition that grants less than 160 KiB to a workgroup
+  // rejects the launch: that raises in the sweep, it never tests less.  The
+  // launch status decides, not the sharedMemPerBlock property.  One table
+  // entry per CU: coverage is every CU.
+  const SweepRun run = sweep_relaunch(cus, 1, max_rounds, d_keys, [&](int) {
+    hipLaunchKernelGGL(lds_integrity_kernel, dim3(grid), dim3(kLdsBlock), 0, 0, a);
+  });
+  const int rounds = run.rounds;
 
-  unsigned long long ctl[kLdsCtlWords], counters[kLdsPhases];
-  d_ctl.download(ctl, kLdsCtlWords);
+  unsigned long long counters[kLdsPhases];
+  const auto taken = log.collect(kLdsMaxRecords);
+  const std::vector<unsigned long long>& ctl = taken.ctl;
   d_counters.download(counters, kLdsPhases);
-  const uint64_t claims = ctl[kLdsCtlClaims];
-  const size_t kept = (size_t)std::min<uint64_t>(claims, (uint64_t)kLdsMaxRecords);
-  std::vector<LdsRecord> recs(kept);
-  if (kept) d_records.download(recs.data(), kept);
 
-  py::list units;
-  for (int key = 0; key < kCovKeys; ++key) {
-    if (h[key] == 0) continue;
-    py::dict u;
-    u["key"] = key;
-    u["xcc"] = key >> 8;
-    u["hw_bits"] = key & 0xFF;
-    u["workgroups"] = h[key];
-    u["fail_mask"] = h[kCovKeys + key];
-    u["hw_id_raw"] = h[2 * kCovKeys + key];
-    u["xcc_id_raw"] = h[3 * kCovKeys + key];
-    units.append(u);
-  }
   py::list records;
-  for (const LdsRecord& r : recs) {
+  for (const LdsRecord& r : taken.records) {
     py::dict e;
     e["key"] = r.key;
     e["block"] = r.block;
@@ -2916,22 +2768,22 @@ static py::dict lds_integrity_check(int device, int reps, int passes,
   }
   py::dict out;
   out["compute_units"] = cus;
-  out["cus_covered"] = cus_covered;
+  out["cus_covered"] = run.tally.cus_covered;
   out["rounds"] = rounds;
   out["blocks"] = grid;
   out["reps"] = reps;
   out["passes"] = passes;
   out["seed"] = seed;
   out["lds_bytes"] = kLdsBytes;
-  out["units"] = units;
+  out["units"] = sweep_unit_list(run.tally, false);
   out["phase_words_verified"] = lds_phase_dict(verified);
   out["phase_words_expected"] = lds_phase_dict(expected);
   out["error_count"] = ctl[kLdsCtlErrors];
   out["xor_or"] = ctl[kLdsCtlXor];
   out["records"] = records;
   // a mismatch that found no record slot left, or found them all claimed
-  out["records_dropped"] = ctl[kLdsCtlErrors] - (uint64_t)kept;
-  out["elapsed_ms"] = elapsed_ms;
+  out["records_dropped"] = ctl[kLdsCtlErrors] - (uint64_t)taken.records.size();
+  out["elapsed_ms"] = run.elapsed_ms;
   return out;
 }
 
@@ -2941,8 +2793,7 @@ static py::dict lds_integrity_reference(uint64_t seed, int block, int rep,
   if (block < 0 || block >= kLdsMaxBlocks || rep < 0 || rep >= kLdsMaxReps)
     throw std::invalid_argument(
         "lds_integrity_reference: block is in [0, 65535], rep in [0, 4095]");
-  if (passes < 1 || passes > kLdsMaxPasses)
-    throw std::invalid_argument("lds_integrity_reference: passes must be in [1, 16]");
+  require_range("lds_integrity_reference", "passes", passes, 1, kLdsMaxPasses);
   const uint32_t b = (uint32_t)block, r = (uint32_t)rep;
   static const char* const kWidthNames[3] = {"b32", "b64", "b128"};
 
@@ -3308,41 +3159,20 @@ static py::dict hl_word_record(int kind, int phase, const char* side,
   return e;
 }
 
-// the result tables of the kernels that compare on the device
-struct HlDeviceTables {
-  DeviceBuf<unsigned long long> ctl{kHbmCtlWords};
-  DeviceBuf<unsigned long long> shards{(size_t)kHbmShards * kHbmShardStride};
-  DeviceBuf<HbmRecord> records;
-  explicit HlDeviceTables(int max_records)
-      : records((size_t)std::max(1, max_records)) {
-    ctl.fill(0);
-    shards.fill(0);
-    records.fill(0);
-  }
-  // after a synchronise: move what the kernels of one phase counted and
-  // recorded into `ph` and `run`, and zero the tables for the next phase
-  void take(int kind, int phase, HlPhase& ph, HlRun& run) {
-    unsigned long long c[kHbmCtlWords];
-    std::vector<unsigned long long> sh(shards.size());
-    ctl.download(c, kHbmCtlWords);
-    shards.download(sh.data(), sh.size());
-    for (int s = 0; s < kHbmShards; ++s)
-      ph.compared += sh[(size_t)s * kHbmShardStride];
-    ph.errors += c[kHbmCtlErrors];
-    run.error_count += c[kHbmCtlErrors];
-    run.xor_or |= c[kHbmCtlXor];
-    const size_t kept =
-        (size_t)std::min<uint64_t>(c[kHbmCtlClaims], (uint64_t)run.room());
-    std::vector<HbmRecord> recs(kept);
-    if (kept) records.download(recs.data(), kept);
-    for (const HbmRecord& r : recs)
-      run.records.append(
-          hl_word_record(kind, phase, "device", r.word, r.expected, r.got));
-    run.dropped += c[kHbmCtlClaims] - kept;
-    ctl.fill(0);
-    shards.fill(0);
-  }
-};
+// after a synchronise: move what the kernels of one phase counted and
+// recorded into `ph` and `run`, and zero the tables for the next phase
+static void hl_take_device(HbmTables& tables, int kind, int phase, HlPhase& ph,
+                           HlRun& run) {
+  const auto log = tables.log.collect(run.room(), true);
+  ph.compared += tables.words_compared(true);
+  ph.errors += log.ctl[kHbmCtlErrors];
+  run.error_count += log.ctl[kHbmCtlErrors];
+  run.xor_or |= log.ctl[kHbmCtlXor];
+  for (const HbmRecord& r : log.records)
+    run.records.append(
+        hl_word_record(kind, phase, "device", r.word, r.expected, r.got));
+  run.dropped += log.claims - log.records.size();
+}
 
 static void hl_take_host(int kind, int phase, const HostlinkTally& t, HlPhase& ph,
                          HlRun& run) {
@@ -3547,8 +3377,7 @@ static py::dict host_link_reference(uint64_t seed, uint64_t threads, int reps,
   // host only: no HIP call
   if (threads > (uint64_t)kHostlinkMaxAtomBlocks * kHostlinkAtomBlock)
     throw std::invalid_argument("host_link_reference: threads is at most 262144");
-  if (reps < 1 || reps > kHostlinkMaxReps)
-    throw std::invalid_argument("host_link_reference: reps must be in [1, 16]");
+  require_range("host_link_reference", "reps", reps, 1, kHostlinkMaxReps);
   if (host_adds < 0 || host_adds > kHostlinkMaxHostAdds ||
       host_adds % kHostlinkAtomCells != 0)
     throw std::invalid_argument(
@@ -3596,7 +3425,7 @@ static py::dict host_link_check(int device, uint64_t nbytes, uint64_t seed,
 
   HlRun run;
   run.max_records = max_records;
-  HlDeviceTables tables(max_records);
+  HbmTables tables(max_records);
   Stream s1, s2;
   Event e1a, e1b, e2a, e2b;
   unsigned fail_mask = 0;
@@ -3649,41 +3478,32 @@ static py::dict host_link_check(int device, uint64_t nbytes, uint64_t seed,
         HIP_CHECK(hipStreamSynchronize(s1.s));
       }
     };
-    // hbm_pattern_kernel over device words [base, base + n) of D
-    const auto device_pass = [&](int hbm_kind, uint64_t base, uint64_t n,
-                                 int phase) {
+    // a pattern kernel's arguments: this phase's hash pattern over n words at
+    // buf, what the log has room for
+    const auto pass_args = [&](uint64_t* buf, uint64_t n, uint64_t base, int phase,
+                               int64_t poison_at) {
       HbmLaunch a;
-      a.buf = D + base;
+      a.buf = buf;
       a.nwords = n;
       a.base = base;
       a.seed = pseed(phase);
       a.poison_xor = poison_xor;
       a.poison_stride = 0;
-      a.poison_word = pword(phase);
-      a.ctl = tables.ctl.get();
-      a.shards = tables.shards.get();
-      a.records = tables.records.get();
-      a.max_records = (uint32_t)run.room();
+      a.poison_word = poison_at;
+      tables.attach(a, run.room());
       a.verify_index = (uint32_t)phase;
       a.pattern = kHbmPatternHash;
-      hbm_launch(hbm_kind, a);
+      return a;
+    };
+    // hbm_pattern_kernel over device words [base, base + n) of D
+    const auto device_pass = [&](int hbm_kind, uint64_t base, uint64_t n,
+                                 int phase) {
+      hbm_launch(hbm_kind, pass_args(D + base, n, base, phase, pword(phase)));
     };
     // hostlink_pattern_kernel over all of H through its device pointer
     const auto host_pass = [&](bool write, int phase) {
-      HbmLaunch a;
-      a.buf = reinterpret_cast<uint64_t*>(hmem.dev);
-      a.nwords = words;
-      a.base = 0;
-      a.seed = pseed(phase);
-      a.poison_xor = poison_xor;
-      a.poison_stride = 0;
-      a.poison_word = write ? -1 : pword(phase);
-      a.ctl = tables.ctl.get();
-      a.shards = tables.shards.get();
-      a.records = tables.records.get();
-      a.max_records = (uint32_t)run.room();
-      a.verify_index = (uint32_t)phase;
-      a.pattern = kHbmPatternHash;
+      const HbmLaunch a = pass_args(reinterpret_cast<uint64_t*>(hmem.dev), words, 0,
+                                    phase, write ? -1 : pword(phase));
       if (write)
         hipLaunchKernelGGL(hostlink_pattern_kernel<true>, dim3(grid),
                            dim3(kHlBlock), 0, 0, a, sub_words);
@@ -3715,7 +3535,7 @@ static py::dict host_link_check(int device, uint64_t nbytes, uint64_t seed,
       timed(ph, (double)nbytes, [&] { copy(D, H, nbytes, hipMemcpyHostToDevice); });
       device_pass(kHbmVerifyInvert, 0, words, kHostlinkH2d);
       HIP_CHECK(hipDeviceSynchronize());
-      tables.take(kind, kHostlinkH2d, ph, run);
+      hl_take_device(tables, kind, kHostlinkH2d, ph, run);
       ph.ms = hl_ms_since(t0);
     }
     {  // bit 1, d2h: H still holds p0, D holds ~p0
@@ -3737,7 +3557,7 @@ static py::dict host_link_check(int device, uint64_t nbytes, uint64_t seed,
         host_pass(false, kHostlinkZcRead);
         HIP_CHECK(hipDeviceSynchronize());
       });
-      tables.take(kind, kHostlinkZcRead, ph, run);
+      hl_take_device(tables, kind, kHostlinkZcRead, ph, run);
       ph.ms = hl_ms_since(t0);
     }
     if (runs & 1u << kHostlinkZcWrite) {  // bit 3: H holds p2 until the kernel ran
@@ -3785,7 +3605,7 @@ static py::dict host_link_check(int device, uint64_t nbytes, uint64_t seed,
       // only words below lo, the host only the rest
       device_pass(kHbmVerifyInvert, 0, lo, kHostlinkDuplex);
       HIP_CHECK(hipDeviceSynchronize());
-      tables.take(kind, kHostlinkDuplex, ph, run);
+      hl_take_device(tables, kind, kHostlinkDuplex, ph, run);
       host_verify(kHostlinkDuplex, lo, words - lo);
       ph.ms = hl_ms_since(t0);
     }
@@ -4125,7 +3945,7 @@ constexpr int kValuWaveRecWords = 1 + kValuConsOps;  // slot + 1 | digests
 
 struct ValuLaunch {
   const uint32_t* tab;
-  uint32_t* slots;      // waves | fail | hw_id | xcc_id, as cov_run_sweep keeps them
+  uint32_t* slots;      // waves | fail | hw_id | xcc_id, as cov_tally reads them
   uint64_t* ctl;        // compared[kValuGroups] | error count
   ValuRecord* records;  // the first kValuMaxRecords mismatches
   uint64_t* wave_recs;  // [round][block][wave][kValuWaveRecWords]
@@ -4144,12 +3964,12 @@ __device__ __noinline__ void valu_mismatch(uint64_t* ctl, ValuRecord* records,
                                            uint32_t simd, int group, int op, int set,
                                            int lane, int rep, uint64_t expected,
                                            uint64_t got) {
-  const uint64_t n = atomicAdd((unsigned long long*)&ctl[kValuCtlErrors], 1ull);
-  if (n >= (uint64_t)kValuMaxRecords) return;
-  ValuRecord& r = records[n];  // n < kValuMaxRecords, the size of the array
-  r.key = key, r.simd = simd, r.group = (uint32_t)group, r.op = (uint32_t)op;
-  r.set = (uint32_t)set, r.lane = (uint32_t)lane, r.rep = (uint32_t)rep, r.pad = 0;
-  r.expected = expected, r.got = got;
+  // the error counter is the claim counter: one atomic per mismatch
+  const ValuRecord r = {key, simd, (uint32_t)group, (uint32_t)op, (uint32_t)set,
+                        (uint32_t)lane, (uint32_t)rep, 0u, expected, got};
+  record_log_claim(RecordLogView<ValuRecord>{(unsigned long long*)&ctl[kValuCtlErrors],
+                                             records, kValuMaxRecords},
+                   [&] { return r; });
 }
 
 template <int OP>
@@ -4370,57 +4190,42 @@ static py::dict valu_coverage_check(int device, int reps, int max_rounds,
     throw std::invalid_argument(
         "valu_coverage_check: poison_all with the consensus bit cannot be "
         "detected: a consensus poisoned everywhere is still a consensus");
-  DeviceBuf<uint64_t> d_ctl, d_wave;
-  DeviceBuf<ValuRecord> d_rec;
-  int round = 0, blocks = 0;
-  py::dict out = cov_run_sweep(
-      "valu_coverage_check", device, reps, max_rounds, poison_key, poison_mask,
-      kValuGroups, valu_build_table(),
-      [&](int cus, uint32_t* tab, uint32_t* slots) {
+  const std::string who = "valu_coverage_check";
+  cov_validate(who, reps, max_rounds, poison_key, poison_mask, kValuGroups);
+  const int cus = cov_select_device(who, device);
+  const int blocks = kCovBlocksPerCu * cus;
+  RecordLog<ValuRecord> log(kValuMaxRecords, kValuCtlWords, kValuCtlErrors);
+  DeviceBuf<uint64_t> d_wave((size_t)max_rounds * blocks * (kCovBlock / 64) *
+                             kValuWaveRecWords);
+  d_wave.fill(0);
+  const SweepRun run = cov_run_sweep(
+      cus, max_rounds, valu_build_table(),
+      [&](int round, uint32_t* tab, uint32_t* slots) {
         ValuLaunch L;
-        L.tab = tab, L.slots = slots, L.ctl = d_ctl.get(), L.records = d_rec.get();
+        L.tab = tab, L.slots = slots, L.ctl = (uint64_t*)log.ctl();
+        L.records = log.view(kValuMaxRecords).records;
         L.wave_recs = d_wave.get();
         L.reps = reps, L.poison_key = poison_key, L.poison_all = poison_all ? 1 : 0;
-        L.round = round++;  // < max_rounds: cov_run_sweep launches no more
+        L.round = round;  // < max_rounds, which is how d_wave is sized
         L.poison_mask = poison_mask;
-        hipLaunchKernelGGL(valu_coverage_kernel, dim3(kCovBlocksPerCu * cus),
-                           dim3(kCovBlock), 0, 0, L);
-      },
-      [&](int cus) {
-        blocks = kCovBlocksPerCu * cus;
-        d_ctl = DeviceBuf<uint64_t>(kValuCtlWords);
-        d_rec = DeviceBuf<ValuRecord>(kValuMaxRecords);
-        d_wave = DeviceBuf<uint64_t>((size_t)max_rounds * blocks * (kCovBlock / 64) *
-                                     kValuWaveRecWords);
-        d_ctl.fill(0);
-        d_rec.fill(0);
-        d_wave.fill(0);
+        hipLaunchKernelGGL(valu_coverage_kernel, dim3(blocks), dim3(kCovBlock), 0,
+                           0, L);
       });
 
-  std::vector<uint64_t> ctl(kValuCtlWords), wave(d_wave.size());
-  std::vector<ValuRecord> rec(kValuMaxRecords);
-  d_ctl.download(ctl.data(), ctl.size());
-  d_rec.download(rec.data(), rec.size());
+  const auto taken = log.collect(kValuMaxRecords);
+  const std::vector<unsigned long long>& ctl = taken.ctl;
+  std::vector<uint64_t> wave(d_wave.size());
   d_wave.download(wave.data(), wave.size());
 
   // per slot, the distinct digest tuples its waves reported
-  std::vector<std::vector<std::vector<uint64_t>>> by_slot(kCovSlots);
-  const size_t n_wave = (size_t)round * blocks * (kCovBlock / 64);
-  for (size_t i = 0; i < n_wave; ++i) {
-    const uint64_t* wr = &wave[i * kValuWaveRecWords];
-    if (wr[0] == 0 || wr[0] > (uint64_t)kCovSlots) continue;
-    std::vector<uint64_t> tuple(wr + 1, wr + kValuWaveRecWords);
-    auto& seen = by_slot[wr[0] - 1];
-    if (std::find(seen.begin(), seen.end(), tuple) == seen.end()) seen.push_back(tuple);
+  const auto by_slot = valu_group_digests(
+      wave.data(), (size_t)run.rounds * blocks * (kCovBlock / 64), kValuWaveRecWords);
+  py::dict out = cov_sweep_dict(run);
+  py::list units = out["units"];  // in the order of run.tally.units
+  for (size_t i = 0; i < run.tally.units.size(); ++i) {
+    const CovUnit& c = run.tally.units[i];
+    units[i]["digests"] = by_slot[c.key * 4 + c.simd];
   }
-  py::list units;
-  for (py::handle h : out["units"]) {
-    py::dict u = py::reinterpret_borrow<py::dict>(h);
-    const int slot = u["key"].cast<int>() * 4 + u["simd"].cast<int>();
-    u["digests"] = by_slot[slot];
-    units.append(u);
-  }
-  out["units"] = units;
 
   py::list compared, items, cons_ops, records;
   for (int g = 0; g < kValuGroups; ++g) {
@@ -4428,10 +4233,8 @@ static py::dict valu_coverage_check(int device, int reps, int max_rounds,
     items.append(valu_items(g));
   }
   for (int op = kValuExactOps; op < kValuOps; ++op) cons_ops.append(kValuOpTable[op].name);
-  const uint64_t errors = ctl[kValuCtlErrors];
-  const uint64_t kept = std::min<uint64_t>(errors, kValuMaxRecords);
-  for (uint64_t i = 0; i < kept; ++i) {
-    const ValuRecord& r = rec[i];
+  const uint64_t errors = taken.claims, kept = taken.records.size();
+  for (const ValuRecord& r : taken.records) {
     py::dict e;
     e["key"] = r.key;
     e["simd"] = r.simd;

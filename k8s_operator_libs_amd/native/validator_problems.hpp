@@ -733,6 +733,85 @@ inline XfAtomExpected xf_atom_expected(uint64_t seed, uint64_t threads, int reps
 }
 
 // ---------------------------------------------------------------------------
+// What the host does with the tables a launch leaves behind: argument range
+// checks, the per-unit tally of a whole-device sweep, the digest grouping of
+// the vector-ALU sweep and the kept / dropped split of a capped record log.
+// ---------------------------------------------------------------------------
+
+constexpr int kCovKeys = 4096;           // placement keys: 4 XCC bits + 8 HW_ID bits
+constexpr int kCovSlots = kCovKeys * 4;  // x 4 SIMDs
+
+// the range checks whose message is the same in every check
+inline void require_range(const std::string& who, const char* name, long value,
+                          long lo, long hi) {
+  if (value < lo || value > hi)
+    throw std::invalid_argument(who + ": " + name + " must be in [" +
+                                std::to_string(lo) + ", " + std::to_string(hi) + "]");
+}
+inline void require_poison_key(const std::string& who, int poison_key) {
+  if (poison_key < -1 || poison_key >= kCovKeys)
+    throw std::invalid_argument(who + ": poison_key out of range");
+}
+
+// One unit that ran at least one wave (simds == 4) or workgroup (simds == 1).
+struct CovUnit {
+  int key, simd;
+  uint32_t waves, fail_mask, hw_id_raw, xcc_id_raw;
+};
+struct CovTally {
+  int cus_covered = 0, slots_covered = 0, failed_slots = 0;
+  long waves_run = 0;
+  bool complete = false;  // every CU of the device, and every SIMD of each
+  std::vector<CovUnit> units;
+};
+
+// `planes` is waves | fail | hw_id | xcc_id, each kCovKeys * simds words, entry
+// key * simds + simd.  The whole-device sweeps keep one entry per SIMD
+// (simds == 4), the LDS check one per CU (simds == 1).
+inline CovTally cov_tally(const uint32_t* planes, int cus, int simds) {
+  const int n = kCovKeys * simds;
+  const uint32_t* waves = planes;
+  CovTally t;
+  for (int key = 0; key < kCovKeys; ++key) {
+    bool any = false;
+    for (int s = 0; s < simds; ++s) {
+      const int slot = key * simds + s;
+      if (waves[slot] == 0) continue;
+      any = true;
+      ++t.slots_covered;
+      t.units.push_back({key, s, waves[slot], planes[n + slot],
+                         planes[2 * n + slot], planes[3 * n + slot]});
+      t.waves_run += waves[slot];
+      t.failed_slots += planes[n + slot] != 0;
+    }
+    t.cus_covered += any;
+  }
+  t.complete = t.cus_covered >= cus && t.slots_covered >= simds * cus;
+  return t;
+}
+
+// Wave records [slot + 1 | digests...] of rec_words words each -> per slot the
+// distinct digest tuples in first-seen order.  A first word of 0 (never
+// written) or above kCovSlots is skipped.
+inline std::vector<std::vector<std::vector<uint64_t>>> valu_group_digests(
+    const uint64_t* recs, size_t n_recs, int rec_words) {
+  std::vector<std::vector<std::vector<uint64_t>>> by_slot(kCovSlots);
+  for (size_t i = 0; i < n_recs; ++i) {
+    const uint64_t* wr = recs + i * (size_t)rec_words;
+    if (wr[0] == 0 || wr[0] > (uint64_t)kCovSlots) continue;
+    std::vector<uint64_t> tuple(wr + 1, wr + rec_words);
+    auto& seen = by_slot[wr[0] - 1];
+    if (std::find(seen.begin(), seen.end(), tuple) == seen.end()) seen.push_back(tuple);
+  }
+  return by_slot;
+}
+
+// records a log of `cap` slots holds after `claims` claims; the rest were dropped
+inline size_t record_log_kept(uint64_t claims, size_t cap) {
+  return (size_t)std::min<uint64_t>(claims, (uint64_t)cap);
+}
+
+// ---------------------------------------------------------------------------
 // LDS data-integrity check: its generators live in a header of their own.
 // ---------------------------------------------------------------------------
 

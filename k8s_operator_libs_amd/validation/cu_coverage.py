@@ -21,7 +21,7 @@ from __future__ import annotations
 
 from typing import Any, Dict, List, Sequence
 
-from .gpu_health import GpuHealthError, load_native_validator
+from .gpu_health import load_native_validator, require_native_validator
 
 SIMDS_PER_CU = 4
 
@@ -112,9 +112,7 @@ def cu_coverage_check(device: int = 0, **kw: Any) -> Dict[str, Any]:
     raw per-slot list as ``units``.  A missing native validator is an error:
     there is no fallback for this check.
     """
-    native = load_native_validator()
-    if native is None:
-        raise GpuHealthError("no native GPU validator available")
+    native = require_native_validator(load_native_validator)
     raw = native.cu_coverage_check(device, **kw)
     summary = summarize_cu_coverage(raw)
     summary["units"] = [dict(u) for u in raw["units"]]

@@ -57,6 +57,16 @@ def load_native_validator():
             return None
 
 
+def require_native_validator(load=load_native_validator):
+    """The native extension for a check that cannot run without it:
+    GpuHealthError where `load` gives None.  A wrapper module passes its own
+    binding of load_native_validator, the name a caller may have replaced."""
+    native = load()
+    if native is None:
+        raise GpuHealthError("no native GPU validator available")
+    return native
+
+
 def smi_probe() -> Dict[str, Any]:
     """amd-smi / rocm-smi process probe: is the driver loaded and are
     devices enumerated?  Returns {'tool': ..., 'ok': bool, 'raw': ...}."""

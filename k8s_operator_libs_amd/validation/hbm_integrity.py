@@ -28,7 +28,7 @@ from __future__ import annotations
 import statistics
 from typing import Any, Dict, List
 
-from .gpu_health import GpuHealthError, load_native_validator
+from .gpu_health import load_native_validator, require_native_validator
 
 MIB = 1 << 20
 PHASE_KINDS = ("fill", "verify_invert", "verify")
@@ -119,9 +119,7 @@ def hbm_integrity_check(device: int = 0, mib: float = 1024.0, **kw: Any) -> Dict
     and ``phases``.  A missing native validator is an error: there is no
     fallback for this check.
     """
-    native = load_native_validator()
-    if native is None:
-        raise GpuHealthError("no native GPU validator available")
+    native = require_native_validator(load_native_validator)
     raw = native.hbm_pattern_check(device, mib_to_bytes(mib), **kw)
     summary = summarize_hbm_integrity(raw)
     summary["records"] = [dict(r) for r in raw["records"]]

@@ -29,7 +29,7 @@ from __future__ import annotations
 
 from typing import Any, Dict, List
 
-from .gpu_health import GpuHealthError, load_native_validator
+from .gpu_health import load_native_validator, require_native_validator
 from .hbm_integrity import flipped_bits, mib_to_bytes
 
 MIB = 1 << 20
@@ -183,9 +183,7 @@ def host_link_check(device: int = 0, mib: float = 64.0, **kw: Any) -> Dict[str, 
     the ``atomics`` tables.  A missing native validator is an error: there is
     no fallback for this check.
     """
-    native = load_native_validator()
-    if native is None:
-        raise GpuHealthError("no native GPU validator available")
+    native = require_native_validator(load_native_validator)
     raw = native.host_link_check(device, mib_to_bytes(mib), **kw)
     summary = summarize_host_link(raw)
     summary["records"] = [dict(r) for r in raw["records"]]

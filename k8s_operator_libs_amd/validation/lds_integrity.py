@@ -36,7 +36,7 @@ from __future__ import annotations
 from typing import Any, Dict, List
 
 from .cu_coverage import _failed_names, decode_key
-from .gpu_health import GpuHealthError, load_native_validator
+from .gpu_health import load_native_validator, require_native_validator
 
 # fail_mask / poison_mask bits, in bit order
 PHASES = ("pattern", "subword", "transpose", "dma", "atomics", "permute")
@@ -165,9 +165,7 @@ def lds_integrity_check(device: int = 0, **kw: Any) -> Dict[str, Any]:
     ``records``.  A missing native validator is an error: there is no
     fallback for this check.
     """
-    native = load_native_validator()
-    if native is None:
-        raise GpuHealthError("no native GPU validator available")
+    native = require_native_validator(load_native_validator)
     raw = native.lds_integrity_check(device, **kw)
     summary = summarize_lds_integrity(raw)
     summary["units"] = [dict(u) for u in raw["units"]]

@@ -20,7 +20,7 @@ from __future__ import annotations
 from typing import Any, Dict
 
 from .cu_coverage import summarize_sweep
-from .gpu_health import GpuHealthError, load_native_validator
+from .gpu_health import load_native_validator, require_native_validator
 
 # fail_mask bits, in bit order: one per same-format pair on 16x16x128, one for
 # the mixed pairs (cbsz != blgp), one for the 32x32x64 shape
@@ -53,9 +53,7 @@ def mx_matrix_check(device: int = 0, **kw: Any) -> Dict[str, Any]:
     raw per-slot list as ``units``.  A missing native validator is an error:
     there is no fallback for this check.
     """
-    native = load_native_validator()
-    if native is None:
-        raise GpuHealthError("no native GPU validator available")
+    native = require_native_validator(load_native_validator)
     raw = native.mx_coverage_check(device, **kw)
     summary = summarize_mx_matrix(raw)
     summary["units"] = [dict(u) for u in raw["units"]]

@@ -22,7 +22,7 @@ from collections import Counter
 from typing import Any, Dict, List, Optional, Tuple
 
 from .cu_coverage import decode_key, summarize_sweep
-from .gpu_health import GpuHealthError, load_native_validator
+from .gpu_health import load_native_validator, require_native_validator
 
 # fail_mask bits, in bit order
 FAIL_BITS = ("f32", "f64", "f16", "int", "convert", "crosslane", "consensus")
@@ -139,9 +139,7 @@ def valu_check(device: int = 0, **kw: Any) -> Dict[str, Any]:
     raw per-slot list as ``units`` and the mismatch records as ``records``.  A
     missing native validator is an error: there is no fallback for this check.
     """
-    native = load_native_validator()
-    if native is None:
-        raise GpuHealthError("no native GPU validator available")
+    native = require_native_validator(load_native_validator)
     raw = native.valu_coverage_check(device, **kw)
     summary = summarize_valu(raw)
     summary["units"] = [dict(u) for u in raw["units"]]

@@ -38,7 +38,7 @@ from __future__ import annotations
 
 from typing import Any, Dict, List
 
-from .gpu_health import GpuHealthError, load_native_validator
+from .gpu_health import load_native_validator, require_native_validator
 
 # poison_mask bit -> the comparison it moves
 POISON_COMPARISONS = (
@@ -198,9 +198,7 @@ def xcd_fabric_check(device: int = 0, **kw: Any) -> Dict[str, Any]:
     ``pairs`` and ``atomics``.  A missing native validator is an error: there
     is no fallback for this check.
     """
-    native = load_native_validator()
-    if native is None:
-        raise GpuHealthError("no native GPU validator available")
+    native = require_native_validator(load_native_validator)
     raw = native.xcd_fabric_check(device, **kw)
     summary = summarize_xcd_fabric(raw)
     summary["records"] = [dict(r) for r in raw["records"]]

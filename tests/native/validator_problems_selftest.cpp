@@ -7,7 +7,10 @@
 // sanitizers.  Beyond that it asserts only what can be stated without the
 // code under test: documented table sizes and layouts, codes decoded by the
 // decoders written here from the format definitions, expected tiles
-// recomputed in double precision, and published splitmix64 values.
+// recomputed in double precision, and published splitmix64 values.  The host
+// side of a launch's results lives there too and is checked on hand-built
+// tables: the per-unit tally of a sweep, the digest grouping of the
+// vector-ALU sweep, the kept count of a record log and the range checks.
 
 #include <cmath>
 #include <cstdint>
@@ -448,9 +451,133 @@ void test_atomics() {
   CHECK(atom_expected_throws(31076, 64, 1));
 }
 
+// planes of a sweep, sized exactly: ASan sees a read past any of them
+struct Planes {
+  int simds;
+  std::vector<uint32_t> v;
+  explicit Planes(int s) : simds(s), v((size_t)4 * kCovKeys * s, 0u) {}
+  void set(int key, int simd, uint32_t waves, uint32_t fail, uint32_t hw,
+           uint32_t xcc) {
+    const size_t n = (size_t)kCovKeys * simds, at = (size_t)key * simds + simd;
+    v[at] = waves, v[n + at] = fail, v[2 * n + at] = hw, v[3 * n + at] = xcc;
+  }
+};
+
+void test_tally() {
+  for (int simds : {4, 1}) {  // the sweeps' form and the per-key (LDS) form
+    Planes p(simds);
+    CovTally t = cov_tally(p.v.data(), 2, simds);
+    CHECK(t.units.empty() && t.cus_covered == 0 && t.slots_covered == 0);
+    CHECK(t.waves_run == 0 && t.failed_slots == 0 && !t.complete);
+
+    // cus = 2: key 0x000 whole, key 0x101 without its last SIMD
+    for (int s = 0; s < simds; ++s) p.set(0x000, s, 1, 0, 0, 0);
+    for (int s = 0; s + 1 < simds; ++s) p.set(0x101, s, 1, 0, 0, 0);
+    t = cov_tally(p.v.data(), 2, simds);
+    if (simds == 4) {
+      CHECK(t.cus_covered == 2 && t.slots_covered == 7 && !t.complete);
+    } else {
+      CHECK(t.cus_covered == 1 && t.slots_covered == 1 && !t.complete);
+    }
+    p.set(0x101, simds - 1, 1, 0, 0, 0);
+    t = cov_tally(p.v.data(), 2, simds);
+    CHECK(t.cus_covered == 2 && t.slots_covered == 2 * simds && t.complete);
+    CHECK(t.waves_run == 2 * simds && t.failed_slots == 0);
+    CHECK(t.units.size() == (size_t)2 * simds);
+    CHECK(!cov_tally(p.v.data(), 3, simds).complete);
+
+    // one slot: counts, and the raw words carried through
+    Planes q(simds);
+    q.set(0x2A5, simds - 1, 3, 0b101u, 0xCAFE0123u, 0x80000002u);
+    t = cov_tally(q.v.data(), 1, simds);
+    CHECK(t.waves_run == 3 && t.failed_slots == 1 && t.units.size() == 1);
+    if (t.units.size() == 1) {
+      const CovUnit& u = t.units[0];
+      CHECK(u.key == 0x2A5 && u.simd == simds - 1 && u.waves == 3);
+      CHECK(u.fail_mask == 0b101u && u.hw_id_raw == 0xCAFE0123u);
+      CHECK(u.xcc_id_raw == 0x80000002u);
+    }
+
+    // the last slot of the planes
+    Planes l(simds);
+    l.set(kCovKeys - 1, simds - 1, 2, 0, 7, 9);
+    t = cov_tally(l.v.data(), 1, simds);
+    CHECK(t.units.size() == 1 && t.cus_covered == 1 && t.waves_run == 2);
+    if (t.units.size() == 1) {
+      CHECK(t.units[0].key == kCovKeys - 1 && t.units[0].simd == simds - 1);
+      CHECK(t.units[0].hw_id_raw == 7 && t.units[0].xcc_id_raw == 9);
+    }
+  }
+}
+
+void test_digest_grouping() {
+  const int W = 3;  // slot + 1 | two digests
+  const std::vector<uint64_t> recs = {
+      0, 1, 1,                            // never written: skipped
+      (uint64_t)kCovSlots + 1, 2, 2,      // above the slots: skipped
+      6, 10, 11,                          // slot 5
+      6, 10, 11,                          // the same tuple again: one entry
+      6, 10, 12,                          // another tuple: kept, second
+      6, 9, 11,                           // and a third, in first-seen order
+      (uint64_t)kCovSlots, 3, 4,          // the last slot
+  };
+  const auto by_slot = valu_group_digests(recs.data(), recs.size() / W, W);
+  CHECK(by_slot.size() == (size_t)kCovSlots);
+  size_t filled = 0;
+  for (const auto& s : by_slot) filled += !s.empty();
+  CHECK(filled == 2);
+  using T = std::vector<uint64_t>;
+  CHECK(by_slot[5].size() == 3);
+  if (by_slot[5].size() == 3) {
+    CHECK(by_slot[5][0] == (T{10, 11}) && by_slot[5][1] == (T{10, 12}));
+    CHECK(by_slot[5][2] == (T{9, 11}));
+  }
+  CHECK(by_slot[kCovSlots - 1].size() == 1);
+  if (by_slot[kCovSlots - 1].size() == 1) CHECK(by_slot[kCovSlots - 1][0] == (T{3, 4}));
+  CHECK(valu_group_digests(recs.data(), 0, W)[5].empty());
+}
+
+bool range_throws(long v, long lo, long hi, const char* want) {
+  try {
+    require_range("some_check", "reps", v, lo, hi);
+  } catch (const std::invalid_argument& e) {
+    return std::strcmp(e.what(), want) == 0;
+  }
+  return false;
+}
+
+void test_record_log_and_ranges() {
+  // kept = min(claims, cap); what a check reports as dropped is its own
+  // count minus kept
+  CHECK(record_log_kept(0, 64) == 0);
+  CHECK(record_log_kept(64, 64) == 64);
+  CHECK(record_log_kept(69, 64) == 64 && 69 - record_log_kept(69, 64) == 5);
+  // a later phase of the host-link check, the room used up before it
+  CHECK(record_log_kept(3, 0) == 0 && 3 - record_log_kept(3, 0) == 3);
+  CHECK(record_log_kept(~0ull, 4096) == 4096);
+
+  CHECK(range_throws(0, 1, 4096, "some_check: reps must be in [1, 4096]"));
+  CHECK(range_throws(64, -1, 63, "some_check: reps must be in [-1, 63]"));
+  CHECK(!range_throws(1, 1, 4096, "") && !range_throws(4096, 1, 4096, ""));
+  for (int key : {-2, kCovKeys}) {
+    bool threw = false;
+    try {
+      require_poison_key("some_check", key);
+    } catch (const std::invalid_argument& e) {
+      threw = std::strcmp(e.what(), "some_check: poison_key out of range") == 0;
+    }
+    CHECK(threw);
+  }
+  require_poison_key("some_check", -1);
+  require_poison_key("some_check", kCovKeys - 1);
+}
+
 }  // namespace
 
 int main() {
+  test_tally();
+  test_digest_grouping();
+  test_record_log_and_ranges();
   test_e4m3();
   test_cov();
   test_mx();
