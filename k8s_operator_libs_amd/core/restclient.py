@@ -68,7 +68,27 @@ def _lower_plural(kind: str) -> str:
     return k + "s"
 
 
+def _pool_max_idle() -> int:
+    """Idle connections worth keeping: one per thread that can be talking
+    to the apiserver at the same moment.  That is the reconcile thread,
+    the eviction and the drain workers (each manager bounds its own) and
+    the per-phase node fan-out."""
+    from ..upgrade.common_manager import CommonUpgradeManager
+    from ..upgrade.drain_manager import DrainManager
+    from ..upgrade.pod_manager import PodManager
+
+    return (1 + PodManager.MAX_CONCURRENT_NODE_WORKERS
+            + DrainManager.MAX_CONCURRENT_NODE_WORKERS
+            + CommonUpgradeManager.MAX_PARALLEL_NODE_OPS)
+
+
 class RestClient(Client):
+    #: plain-HTTP requests share keep-alive connections between threads
+    #: through ``_wire.Pool`` when the extension has it, so a worker thread
+    #: started for one node does not dial a connection of its own; False
+    #: keeps one socket per thread (``_fast_local``)
+    USE_POOL = True
+
     def __init__(
         self,
         base_url: str,
@@ -93,6 +113,7 @@ class RestClient(Client):
         # TLS endpoints (real apiservers) stay on httpx.
         self._fast_netloc = None
         self._wire = None
+        self._pool = None
         if self.base_url.startswith("http://"):
             import urllib.parse
 
@@ -102,6 +123,10 @@ class RestClient(Client):
             # native wire path (plain HTTP only; TLS never takes it)
             self._wire = _load_wire()
             self._wire_heads: Dict[tuple, bytes] = {}
+            if self._wire is not None and hasattr(self._wire, "Pool"):
+                self._pool = self._wire.Pool(
+                    *self._fast_netloc, max_idle=_pool_max_idle(),
+                    connect_timeout=timeout)
         self._kinds = dict(_KIND_INFO)
         if extra_kinds:
             self._kinds.update(extra_kinds)
@@ -147,6 +172,12 @@ class RestClient(Client):
         if params:
             path = f"{path}?{urllib.parse.urlencode(params)}"
         head = self._wire_head(headers)
+        pool = self._pool if self.USE_POOL else None
+        if pool is not None:
+            try:
+                return self._pool_request(pool, method, path, head, content)
+            except _PoolClosed:
+                pass  # close() won the race: as after close() without a pool
         sock = getattr(self._fast_local, "sock", None)
         for attempt in (0, 1):
             try:
@@ -182,6 +213,38 @@ class RestClient(Client):
                 if not reusable:
                     self._wire_drop(sock)
                 return _FastResponse(status, data)
+        raise AssertionError("unreachable")
+
+    def _pool_request(self, pool, method: str, path: str, head: bytes,
+                      content):
+        """``_wire_request`` over a connection borrowed from the client's
+        pool for this one exchange.  The fd stays the pool's: it goes back
+        with ``checkin`` whatever happened, and the pool keeps it only
+        after a complete, reusable response.  A connection from the idle
+        list that turns out dead is replaced by a fresh dial once, as the
+        thread-local path reconnects once, but only for a reset or a
+        broken pipe; a freshly dialled one is not retried."""
+        for fresh in (False, True):
+            try:
+                fd, reused = pool.checkout(fresh)
+            except RuntimeError as exc:
+                raise _PoolClosed() from exc
+            keep = False
+            try:
+                status, data, keep = self._wire.exchange(
+                    fd, method, path, head, content, self._timeout)
+            except ValueError as exc:
+                # malformed framing: not resent (see _wire_request)
+                raise _http_client.HTTPException(str(exc)) from exc
+            except (ConnectionResetError, BrokenPipeError):
+                if not reused:
+                    raise
+            else:
+                return _FastResponse(status, data)
+            finally:
+                # also on timeout and on an interruption (Ctrl-C): a
+                # half-read response is closed, not left for the next user
+                pool.checkin(fd, keep)
         raise AssertionError("unreachable")
 
     def _wire_drop(self, sock) -> None:
@@ -507,6 +570,13 @@ class RestClient(Client):
                     pass
                 self._fast_local.conn = None
             self._wire_drop(getattr(self._fast_local, "sock", None))
+            pool, self._pool = self._pool, None
+            if pool is not None:
+                pool.close()
+
+
+class _PoolClosed(Exception):
+    """The client was closed while a request was on its way to the pool."""
 
 
 class _FastResponse:

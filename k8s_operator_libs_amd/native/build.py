@@ -19,6 +19,7 @@ JSONOPS_OUTPUT = os.path.join(PKG_DIR, "_jsonops.so")
 WIRE_SOURCES = (
     os.path.join(PKG_DIR, "wire.cpp"),
     os.path.join(PKG_DIR, "wire_core.hpp"),
+    os.path.join(PKG_DIR, "wire_pool.hpp"),
     os.path.join(PKG_DIR, "wire_stream.hpp"),
 )
 WIRE_OUTPUT = os.path.join(PKG_DIR, "_wire.so")
@@ -29,7 +30,7 @@ CXX = os.environ.get("CXX", "g++")
 
 def validator_sources() -> list:
     """gpu_validator.hip and its headers: every ``*.hpp`` next to it except
-    the two ``wire_*.hpp`` that belong to ``_wire.so``."""
+    the ``wire_*.hpp`` that belong to ``_wire.so``."""
     wire = {os.path.basename(p) for p in WIRE_SOURCES}
     return [SOURCE] + sorted(
         os.path.join(PKG_DIR, name) for name in os.listdir(PKG_DIR)

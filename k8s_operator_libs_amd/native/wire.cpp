@@ -4,10 +4,15 @@
 // of the response, and the pure-Python line iteration of the watch stream)
 // is where the cached-substrate reconcile loop spends its time
 // (docs/performance.md).  This CPython extension does the framing natively
-// on a socket the Python side owns:
+// on a socket the caller hands in:
 //
 //   exchange(fd, method, path, header_bytes, body, timeout)
 //       -> (status, body_bytes, reusable)
+//   Pool(host, port, max_idle, connect_timeout)
+//       .checkout() -> (fd, reused), .checkin(fd, reusable)
+//       keep-alive connections shared by all threads of a client: a thread
+//       that lives for one request reuses what another left behind and
+//       pays no dial (docs/performance.md)
 //   LineReader(fd).read_head(timeout) -> status
 //   LineReader(fd).readline(timeout)  -> bytes | None
 //   parse_request_head(data)          -> None | (method, target, ...)
@@ -22,12 +27,16 @@
 //   LinePump(fd | LineReader).wait(seen_seq, timeout) -> seq, .drain()
 //       client side: one native thread per stream reads head and lines
 //
-// Rules: the fd belongs to the Python socket object and is never closed
-// here; every wait is poll()+recv()/send() with the remaining deadline and
-// with the GIL released; EINTR re-takes the GIL and runs signal handlers;
-// the native threads never take the GIL.  Parsing lives in wire_core.hpp,
-// backlog, line framing and the pending-line queue in wire_stream.hpp (no
-// Python, no sockets).
+// Rules: an fd passed in is borrowed and is never closed here, whether it
+// belongs to a Python socket object or to a Pool.  The one exception to
+// "never close" is the Pool: it opens its own fds and always closes them
+// itself, at checkin(), close() or when it is freed, so that nobody else
+// has to (or may).  Every wait is poll()+recv()/send()/connect() with the
+// remaining deadline and with the GIL released; EINTR re-takes the GIL and
+// runs signal handlers; the native threads never take the GIL.  Parsing
+// and response framing live in wire_core.hpp, backlog, line framing and the
+// pending-line queue in wire_stream.hpp (no Python, no sockets), the pool
+// in wire_pool.hpp (sockets, no Python).
 
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
@@ -50,6 +59,7 @@
 #include <unistd.h>
 
 #include "wire_core.hpp"
+#include "wire_pool.hpp"
 #include "wire_stream.hpp"
 
 namespace {
@@ -195,10 +205,6 @@ PyObject* raise_timeout() {
   return nullptr;
 }
 
-bool status_has_no_body(int status) {
-  return status == 204 || status == 304;
-}
-
 // bytes | str | None  ->  pointer/length (str is UTF-8 encoded in place)
 bool as_buffer(PyObject* obj, const char** p, Py_ssize_t* n, bool* present) {
   *present = true;
@@ -259,89 +265,33 @@ PyObject* py_exchange(PyObject* /*self*/, PyObject* args) {
   if (io == kIoTimeout) return raise_timeout();
   if (io != kIoOk) return nullptr;
 
-  wire::HeadParser head_parser(wire::HeadParser::kResponse);
-  wire::ChunkedDecoder chunked;
-  std::string out;
-  enum { kHead, kLength, kChunked, kUntilClose, kComplete } phase = kHead;
-  size_t remaining = 0;
-  bool reusable = true;
-  bool got_any = false;
+  wire::ResponseReader reader(is_head);
   char buf[kRecvBuf];  // on the stack: no allocation per request
 
-  while (phase != kComplete) {
+  while (!reader.done()) {
     size_t got = 0;
     io = recv_some(fd, buf, sizeof buf, dl, &got);
     if (io == kIoTimeout) return raise_timeout();
     if (io != kIoOk) return nullptr;
     if (got == 0) {
-      if (phase == kUntilClose) {
-        phase = kComplete;
-        break;
-      }
+      if (reader.peer_closed()) break;
+      bool got_any = reader.started();
       PyErr_SetString(got_any ? PyExc_ConnectionError
                               : PyExc_ConnectionResetError,
                       got_any ? "peer closed the connection mid-response"
                               : "peer closed the connection without a response");
       return nullptr;
     }
-    got_any = true;
-    const char* p = buf;
-    size_t n = got;
-    while (n > 0 && phase != kComplete) {
-      size_t used = 0;
-      if (phase == kHead) {
-        int st = head_parser.feed(p, n, &used);
-        if (st < 0) return raise_wire_error(st);
-        if (st == wire::kDone) {
-          int code = head_parser.status;
-          if (code >= 100 && code < 200 && code != 101) {
-            head_parser.reset();  // interim response: skip it
-          } else {
-            if (!head_parser.keep_alive()) reusable = false;
-            if (is_head || status_has_no_body(code)) {
-              phase = kComplete;
-            } else if (head_parser.chunked) {
-              phase = kChunked;
-            } else if (head_parser.has_content_length) {
-              remaining = head_parser.content_length;
-              if (remaining == 0) {
-                phase = kComplete;
-              } else {
-                phase = kLength;
-                // cap the up-front reservation: the length is peer-supplied
-                out.reserve(remaining < (size_t(1) << 26) ? remaining
-                                                          : (size_t(1) << 26));
-              }
-            } else {
-              phase = kUntilClose;
-              reusable = false;
-            }
-          }
-        }
-      } else if (phase == kLength) {
-        used = n < remaining ? n : remaining;
-        out.append(p, used);
-        remaining -= used;
-        if (remaining == 0) phase = kComplete;
-      } else if (phase == kChunked) {
-        int st = chunked.feed(p, n, &used, &out);
-        if (st < 0) return raise_wire_error(st);
-        if (st == wire::kDone) phase = kComplete;
-      } else {  // kUntilClose
-        used = n;
-        out.append(p, used);
-      }
-      p += used;
-      n -= used;
-    }
-    if (n > 0) reusable = false;  // bytes past the response: do not reuse
+    int st = reader.feed(buf, got);
+    if (st < 0) return raise_wire_error(st);
   }
 
+  const std::string& out = reader.body();
   PyObject* body_bytes =
       PyBytes_FromStringAndSize(out.data(), Py_ssize_t(out.size()));
   if (!body_bytes) return nullptr;
-  PyObject* res = Py_BuildValue("(iNO)", head_parser.status, body_bytes,
-                                reusable ? Py_True : Py_False);
+  PyObject* res = Py_BuildValue("(iNO)", reader.status(), body_bytes,
+                                reader.reusable() ? Py_True : Py_False);
   return res;
 }
 
@@ -1124,6 +1074,194 @@ PyTypeObject StreamWriterType = {
 };
 
 // ---------------------------------------------------------------------------
+// Pool (keep-alive connections shared by every thread of a client)
+// ---------------------------------------------------------------------------
+
+struct PoolObject {
+  PyObject_HEAD
+  wire::Pool* pool;
+};
+
+void pool_dealloc(PoolObject* self) {
+  delete self->pool;  // closes the idle fds
+  Py_TYPE(self)->tp_free(reinterpret_cast<PyObject*>(self));
+}
+
+int pool_init(PoolObject* self, PyObject* args, PyObject* kw) {
+  static const char* names[] = {"host", "port", "max_idle", "connect_timeout",
+                                nullptr};
+  const char* host;
+  int port;
+  Py_ssize_t max_idle = 8;
+  PyObject* timeout_obj = Py_None;
+  if (!PyArg_ParseTupleAndKeywords(args, kw, "si|nO",
+                                   const_cast<char**>(names), &host, &port,
+                                   &max_idle, &timeout_obj))
+    return -1;
+  if (self->pool != nullptr) {
+    PyErr_SetString(PyExc_RuntimeError, "Pool is already initialised");
+    return -1;
+  }
+  if (port < 0 || port > 65535 || max_idle < 0) {
+    PyErr_SetString(PyExc_ValueError,
+                    "port must be 0..65535 and max_idle >= 0");
+    return -1;
+  }
+  double timeout_s;
+  if (!parse_timeout(timeout_obj, &timeout_s)) return -1;
+  try {
+    self->pool = new wire::Pool(host, port, size_t(max_idle), timeout_s);
+  } catch (const std::bad_alloc&) {
+    PyErr_NoMemory();
+    return -1;
+  }
+  return 0;
+}
+
+bool pool_enter(PoolObject* self) {
+  if (self->pool == nullptr) {
+    PyErr_SetString(PyExc_RuntimeError, "Pool is not initialised");
+    return false;
+  }
+  return true;
+}
+
+// a signal interrupted the dial: take the GIL back and run the handlers
+bool pool_on_eintr(void*) {
+  PyGILState_STATE gil = PyGILState_Ensure();
+  bool go_on = PyErr_CheckSignals() == 0;
+  PyGILState_Release(gil);
+  return go_on;
+}
+
+PyObject* pool_checkout_impl(PoolObject* self, PyObject* args) {
+  int fresh = 0;
+  if (!PyArg_ParseTuple(args, "|p", &fresh)) return nullptr;
+  if (!pool_enter(self)) return nullptr;
+  // the idle list first: a mutex and a zero-timeout poll, nothing to wait for
+  wire::Pool::Lease lease;
+  if (!fresh) lease = self->pool->take_idle();
+  if (lease.fd < 0 && lease.error == wire::Pool::kOk) {
+    Py_BEGIN_ALLOW_THREADS
+    lease = self->pool->dial(pool_on_eintr, nullptr);
+    Py_END_ALLOW_THREADS
+  }
+  switch (lease.error) {
+    case wire::Pool::kOk:
+      return Py_BuildValue("(iO)", lease.fd,
+                           lease.reused ? Py_True : Py_False);
+    case wire::Pool::kClosed:
+      PyErr_SetString(PyExc_RuntimeError, "Pool is closed");
+      return nullptr;
+    case wire::Pool::kResolve: {
+      PyObject* gaierror = nullptr;
+      PyObject* mod = PyImport_ImportModule("socket");
+      if (mod != nullptr) {
+        gaierror = PyObject_GetAttrString(mod, "gaierror");
+        Py_DECREF(mod);
+      }
+      if (gaierror == nullptr) return nullptr;
+      PyObject* val = Py_BuildValue("(is)", lease.code, gai_strerror(lease.code));
+      if (val != nullptr) {
+        PyErr_SetObject(gaierror, val);  // an OSError subclass
+        Py_DECREF(val);
+      }
+      Py_DECREF(gaierror);
+      return nullptr;
+    }
+    case wire::Pool::kTimeout:
+      return raise_timeout();
+    case wire::Pool::kInterrupted:
+      return nullptr;  // the signal handler's exception is set
+    default:
+      errno = lease.code;
+      return PyErr_SetFromErrno(PyExc_OSError);
+  }
+}
+
+PyObject* pool_checkout(PoolObject* self, PyObject* args) {
+  try {
+    return pool_checkout_impl(self, args);
+  } catch (const std::bad_alloc&) {
+    return PyErr_NoMemory();
+  }
+}
+
+PyObject* pool_checkin(PoolObject* self, PyObject* args) {
+  int fd, reusable;
+  if (!PyArg_ParseTuple(args, "ip", &fd, &reusable)) return nullptr;
+  if (!pool_enter(self)) return nullptr;
+  try {
+    self->pool->checkin(fd, reusable != 0);
+  } catch (const std::bad_alloc&) {
+    close(fd);  // the idle list could not grow: the fd is still the pool's
+  }
+  Py_RETURN_NONE;
+}
+
+PyObject* pool_close(PoolObject* self, PyObject*) {
+  if (!pool_enter(self)) return nullptr;
+  self->pool->close();
+  Py_RETURN_NONE;
+}
+
+PyObject* pool_stats(PoolObject* self, PyObject*) {
+  if (!pool_enter(self)) return nullptr;
+  wire::PoolStats st = self->pool->stats();
+  return Py_BuildValue("{s:K,s:K,s:K,s:n}", "dials",
+                       static_cast<unsigned long long>(st.dials), "reuses",
+                       static_cast<unsigned long long>(st.reuses),
+                       "stale_discards",
+                       static_cast<unsigned long long>(st.stale_discards),
+                       "idle", Py_ssize_t(st.idle));
+}
+
+PyObject* pool_get_max_idle(PoolObject* self, void*) {
+  if (!pool_enter(self)) return nullptr;
+  return PyLong_FromSize_t(self->pool->max_idle());
+}
+
+PyObject* pool_get_closed(PoolObject* self, void*) {
+  if (!pool_enter(self)) return nullptr;
+  return PyBool_FromLong(self->pool->closed());
+}
+
+PyMethodDef pool_methods[] = {
+    {"checkout", reinterpret_cast<PyCFunction>(pool_checkout), METH_VARARGS,
+     "checkout(fresh=False) -> (fd, reused).  The most recently used idle "
+     "connection that is still quiet (reused=True), else (or with fresh) a "
+     "new one, dialled with the GIL released.  The fd stays the pool's: pass it to exchange() and "
+     "give it back with checkin(), exactly once, never close it.  OSError "
+     "(TimeoutError, socket.gaierror) when the dial fails; RuntimeError "
+     "once the pool is closed."},
+    {"checkin", reinterpret_cast<PyCFunction>(pool_checkin), METH_VARARGS,
+     "checkin(fd, reusable).  Give a checked-out fd back.  It is kept for "
+     "the next checkout() only when reusable is true (the response was "
+     "complete and exchange() said reusable), the pool is open and fewer "
+     "than max_idle are idle; otherwise the pool closes it."},
+    {"close", reinterpret_cast<PyCFunction>(pool_close), METH_NOARGS,
+     "close().  Close the idle connections; one checked out now is closed "
+     "when it comes back.  checkout() raises from here on."},
+    {"stats", reinterpret_cast<PyCFunction>(pool_stats), METH_NOARGS,
+     "stats() -> {'dials', 'reuses', 'stale_discards', 'idle'}."},
+    {nullptr, nullptr, 0, nullptr},
+};
+
+PyGetSetDef pool_getset[] = {
+    {"max_idle", reinterpret_cast<getter>(pool_get_max_idle), nullptr,
+     "most connections kept idle", nullptr},
+    {"closed", reinterpret_cast<getter>(pool_get_closed), nullptr,
+     "True after close()", nullptr},
+    {nullptr, nullptr, nullptr, nullptr, nullptr},
+};
+
+PyTypeObject PoolType = {
+    PyVarObject_HEAD_INIT(nullptr, 0)
+    "_wire.Pool",                 /* tp_name */
+    sizeof(PoolObject),           /* tp_basicsize */
+};
+
+// ---------------------------------------------------------------------------
 // module
 // ---------------------------------------------------------------------------
 
@@ -1205,8 +1343,28 @@ PyMODINIT_FUNC PyInit__wire(void) {
   LinePumpType.tp_methods = linepump_methods;
   LinePumpType.tp_getset = linepump_getset;
   if (PyType_Ready(&LinePumpType) < 0) return nullptr;
+  PoolType.tp_flags = Py_TPFLAGS_DEFAULT;
+  PoolType.tp_doc =
+      "Pool(host, port, max_idle=8, connect_timeout=None): keep-alive "
+      "connections to one plain-HTTP endpoint, shared by every thread.  The "
+      "pool opens its sockets itself and is the only one to close them; "
+      "checkout() lends an fd to one exchange() at a time.  A forked child "
+      "starts with an empty pool.";
+  PoolType.tp_new = PyType_GenericNew;
+  PoolType.tp_init = reinterpret_cast<initproc>(pool_init);
+  PoolType.tp_dealloc = reinterpret_cast<destructor>(pool_dealloc);
+  PoolType.tp_methods = pool_methods;
+  PoolType.tp_getset = pool_getset;
+  if (PyType_Ready(&PoolType) < 0) return nullptr;
   PyObject* m = PyModule_Create(&wire_module);
   if (!m) return nullptr;
+  Py_INCREF(&PoolType);
+  if (PyModule_AddObject(m, "Pool",
+                         reinterpret_cast<PyObject*>(&PoolType)) < 0) {
+    Py_DECREF(&PoolType);
+    Py_DECREF(m);
+    return nullptr;
+  }
   Py_INCREF(&LinePumpType);
   if (PyModule_AddObject(m, "LinePump",
                          reinterpret_cast<PyObject*>(&LinePumpType)) < 0) {

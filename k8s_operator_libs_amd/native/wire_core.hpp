@@ -381,6 +381,105 @@ class ChunkedDecoder {
 };
 
 // ---------------------------------------------------------------------------
+// One whole response to one request: head (interim 1xx responses skipped),
+// then the body by Content-Length, chunked or read-until-close framing.
+// ---------------------------------------------------------------------------
+
+class ResponseReader {
+ public:
+  // head_request: the request was a HEAD, so the response carries no body
+  explicit ResponseReader(bool head_request)
+      : head_(HeadParser::kResponse), head_request_(head_request) {}
+
+  // Consume bytes as they arrive.  kNeedMore, kDone (status/body/reusable
+  // are final) or an error.  Bytes past the end of the response are not
+  // consumed; they make the connection not reusable.
+  int feed(const char* p, size_t n) {
+    if (n > 0) started_ = true;
+    while (n > 0 && phase_ != kComplete) {
+      size_t used = 0;
+      if (phase_ == kHead) {
+        int st = head_.feed(p, n, &used);
+        if (st < 0) return st;
+        if (st == kDone) on_head();
+      } else if (phase_ == kLength) {
+        used = n < remaining_ ? n : remaining_;
+        body_.append(p, used);
+        remaining_ -= used;
+        if (remaining_ == 0) phase_ = kComplete;
+      } else if (phase_ == kChunked) {
+        int st = chunked_.feed(p, n, &used, &body_);
+        if (st < 0) return st;
+        if (st == kDone) phase_ = kComplete;
+      } else {  // kUntilClose
+        used = n;
+        body_.append(p, used);
+      }
+      p += used;
+      n -= used;
+    }
+    if (n > 0) reusable_ = false;  // bytes past the response: do not reuse
+    return phase_ == kComplete ? kDone : kNeedMore;
+  }
+
+  // The peer closed the connection.  True when that ends the response (a
+  // read-until-close body); false when it cut the response short.
+  bool peer_closed() {
+    if (phase_ == kUntilClose) phase_ = kComplete;
+    return phase_ == kComplete;
+  }
+
+  bool done() const { return phase_ == kComplete; }
+  bool started() const { return started_; }  // any byte of a response seen
+  int status() const { return head_.status; }
+  bool reusable() const { return reusable_; }
+  std::string& body() { return body_; }
+
+ private:
+  static bool status_has_no_body(int status) {
+    return status == 204 || status == 304;
+  }
+
+  void on_head() {
+    int code = head_.status;
+    if (code >= 100 && code < 200 && code != 101) {
+      head_.reset();  // interim response: skip it
+      return;
+    }
+    if (!head_.keep_alive()) reusable_ = false;
+    if (head_request_ || status_has_no_body(code)) {
+      phase_ = kComplete;
+    } else if (head_.chunked) {
+      phase_ = kChunked;
+    } else if (head_.has_content_length) {
+      remaining_ = head_.content_length;
+      if (remaining_ == 0) {
+        phase_ = kComplete;
+      } else {
+        phase_ = kLength;
+        // cap the up-front reservation: the length is peer-supplied
+        body_.reserve(remaining_ < (size_t(1) << 26) ? remaining_
+                                                     : (size_t(1) << 26));
+      }
+    } else {
+      phase_ = kUntilClose;
+      reusable_ = false;
+    }
+  }
+
+  enum Phase { kHead, kLength, kChunked, kUntilClose, kComplete };
+
+  HeadParser head_;
+  ChunkedDecoder chunked_;
+  std::string body_;
+  Phase phase_ = kHead;
+  size_t remaining_ = 0;
+  bool head_request_;
+  bool reusable_ = true;
+  bool started_ = false;
+};
+
+// ---------------------------------------------------------------------------
 // Line splitter: complete LF-terminated lines, blank ones skipped, a partial
 // line carried across feeds.
 // ---------------------------------------------------------------------------
